@@ -7,10 +7,16 @@ data of the HIGGS shape, random-init trees; no network for the real CSV).
 The train AUC is reported for the SYNTHETIC task and is not comparable to
 real-HIGGS AUC numbers; the rounds/s timing is the measured metric.
 
-On a single GPU the emitted JSON also carries ``config.secondary_config``:
-the 100M x 200 reg:squarederror single-GPU form of BASELINE config 3,
-measured back-to-back in the same process (stdout stays ONE JSON line,
-per the driver contract).
+A plain run sets up, warms up, times ``--steps`` rounds and prints ONE JSON
+line. With ``--full`` on a single GPU the emitted JSON also carries
+``config.secondary_config``: the 100M x 200 reg:squarederror single-GPU
+form of BASELINE config 3, measured back-to-back in the same process
+(stdout stays ONE JSON line, per the driver contract).
+
+``--dump-outputs DIR`` writes what the last timed round computed - the
+tree it returned and the training margins it left behind - as
+``DIR/<name>.npy`` so two builds can be compared output for output (the
+synthetic inputs are seeded, so equal arguments give equal inputs).
 
 Single process: `python bench.py --gpus 1 --steps K --warmup W`.
 Multi-GPU: launched by the driver as one rank per GPU via
@@ -44,6 +50,44 @@ def synth_higgs(n_rows: int, n_features: int, device, seed: int):
     return X, y
 
 
+# --dump-outputs budget: 64 MB in all; the margins get 48 MB of it and
+# the single tree of the last round is a few hundred KB at most
+DUMP_MARGIN_MAX_ELEMS = 12_000_000
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(dump_dir: str, trees, margin: torch.Tensor):
+    """Write the last timed round's results as float32/float64 .npy files.
+
+    `trees` is what BoostingEngine.update() returned in that round and
+    `margin` the per-row training margins after it. Margins larger than
+    the budget are written as a fixed seeded sample of their (flattened)
+    elements, with the sampled positions alongside.
+    """
+    os.makedirs(dump_dir, exist_ok=True)
+    flat = margin.detach().reshape(-1)
+    if flat.numel() > DUMP_MARGIN_MAX_ELEMS:
+        rng = np.random.RandomState(DUMP_SAMPLE_SEED)
+        idx = np.sort(rng.randint(
+            0, flat.numel(), size=DUMP_MARGIN_MAX_ELEMS // 4
+        ).astype(np.int64))
+        sel = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(dump_dir, "margin_sample_index.npy"),
+                idx.astype(np.float64))
+        np.save(os.path.join(dump_dir, "margin_sample.npy"),
+                sel.cpu().numpy().astype(np.float32))
+    else:
+        np.save(os.path.join(dump_dir, "margin.npy"),
+                flat.cpu().numpy().astype(np.float32))
+    for i, t in enumerate(trees):
+        for field in ("feat", "thr", "left", "default_left", "value",
+                      "gain", "cover"):
+            np.save(
+                os.path.join(dump_dir, f"last_tree{i}_{field}.npy"),
+                np.asarray(getattr(t, field)).astype(np.float32),
+            )
+
+
 def run_config(
     coll,
     device,
@@ -57,9 +101,11 @@ def run_config(
     max_bin: int,
     steps: int,
     warmup: int,
+    dump_dir=None,
 ):
     """Train `steps` timed rounds on one synthetic config; returns the
-    result dict (rank 0) or None."""
+    result dict (rank 0) or None. With `dump_dir`, rank 0 also writes the
+    last timed round's outputs there (after the timed region)."""
     from xgboost_ray_amd.engine.metrics import get_metric
     from xgboost_ray_amd.engine.quantile import BinnedMatrix
     from xgboost_ray_amd.engine.trainer import BoostingEngine
@@ -99,8 +145,9 @@ def run_config(
     if use_gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last_trees = []
     for _ in range(steps):
-        engine.update()
+        last_trees = engine.update()
     if use_gpu:
         torch.cuda.synchronize()
     coll.barrier()
@@ -114,6 +161,9 @@ def run_config(
     if world > 1:
         coll.allreduce_(el_t, op="max")
     elapsed_max = float(el_t[0])
+
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, last_trees, engine.margin)
 
     # final train quality (the metric's second half; rmse for regression)
     quality_name = "auc" if objective == "binary:logistic" else "rmse"
@@ -185,9 +235,17 @@ def main():
     p.add_argument("--objective", default="binary:logistic",
                    choices=["binary:logistic", "reg:squarederror"])
     p.add_argument("--cpu", action="store_true", help="force CPU (debug)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure the 100Mx200 secondary config "
+                        "(1 GPU, default shape)")
     p.add_argument("--skip-secondary", action="store_true",
-                   help="skip the 100Mx200 secondary config")
+                   help="with --full: skip the 100Mx200 secondary config")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed round's outputs (tree + "
+                        "training margins) as DIR/<name>.npy")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
 
     import torch.distributed as dist
 
@@ -228,13 +286,14 @@ def main():
         rows=args.rows, features=args.features, objective=args.objective,
         max_depth=args.max_depth, max_bin=args.max_bin,
         steps=args.steps, warmup=args.warmup,
+        dump_dir=args.dump_outputs,
     )
 
-    # Secondary config (single-GPU form of BASELINE config 3):
+    # Secondary config (single-GPU form of BASELINE config 3), --full only:
     # 100M x 200 reg:squarederror. Only on 1 GPU at default shape, so
     # multi-GPU SCALE runs stay a single clean timed region.
     run_secondary = (
-        use_gpu and world == 1 and not args.skip_secondary
+        args.full and use_gpu and world == 1 and not args.skip_secondary
         and args.rows == 11_000_000 and args.features == 28
         and args.objective == "binary:logistic"
     )

@@ -1,7 +1,7 @@
 """Extended sklearn-API parity suite.
 
 Independently written against the behaviors the reference exercises in
-/root/reference/xgboost_ray/tests/test_sklearn.py (its adaptation of
+xgboost_ray/tests/test_sklearn.py (its adaptation of
 XGBoost's own sklearn suite): stacking, feature selection, parameter
 plumbing, custom objectives, validation weights, save/load, resume,
 constraint parameters, pandas input, base-margin boosting, ranking.

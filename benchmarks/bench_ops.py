@@ -32,7 +32,69 @@ def timeit(name, fn, reps=20):
     return dt
 
 
+def bench_leaf_quantile(n=11_000_000, K=256, F=28, n_round=2_000_000):
+    """leaf_quantile_hist: the four radix-select passes over K leaf
+    segments (both LDS schemes, unit and int64 weights), against
+    update_margins over the same segments - both make one pass over ridx
+    with a gathered 4-byte access - and a reg:quantileerror round against
+    a reg:squarederror round of the same shape."""
+    from xgboost_ray_amd.engine.trainer import BoostingEngine
+
+    dev = torch.device("cuda")
+    gen = torch.Generator(device=dev).manual_seed(0)
+    resid = torch.randn(n, device=dev, generator=gen)
+    W = torch.randint(0, 2**30 + 1, (n,), device=dev, generator=gen)
+    ridx = torch.randperm(n, device=dev).to(torch.int32)
+    cut = torch.sort(
+        torch.randint(1, n - 1, (K - 1,), generator=gen, device=dev)
+    )[0].cpu()
+    starts = torch.cat([torch.tensor([0]), cut]).long()
+    counts = torch.cat([cut, torch.tensor([n])]).long() - starts
+    lv = np.random.RandomState(0).randn(K).astype(np.float32)
+    m = torch.zeros(n, device=dev)
+    t_um = timeit("update_margins K=%d" % K,
+                  lambda: ops.update_margins(m, ridx, starts, counts, lv))
+    # prefixes of the real select (median of every leaf)
+    q, _ = ops.leaf_quantile_select(resid, None, ridx, starts, counts, 0.5)
+    key = q.view(np.uint32).astype(np.int64)
+    key = np.where(key & 0x80000000, key ^ 0xFFFFFFFF, key | 0x80000000)
+    hist = torch.zeros((K, 256), dtype=torch.int64, device=dev)
+    for wname, wt, nbytes in (("unit", None, 8), ("int64 W", W, 16)):
+        total = 0.0
+        for p in range(4):
+            prefix = torch.from_numpy(
+                (key >> (32 - 8 * p)) if p else np.zeros(K, np.int64))
+            dt = timeit(
+                f"lqh {wname} pass{p}",
+                lambda: ops.leaf_quantile_hist(
+                    resid, wt, ridx, starts, counts, prefix, p, hist),
+            )
+            # pass 0 touches ridx + resid (+ W) of every row; later
+            # passes skip W for the rows that fail the prefix test
+            if p == 0:
+                print(f"    achieved {n * nbytes / dt / 1e6:8.1f} GB/s "
+                      f"({nbytes} B/row)")
+            total += dt
+        print(f"  lqh {wname}: 4 passes {total:.3f} ms = "
+              f"{total / t_um:.2f} x update_margins")
+
+    X = torch.randn(n_round, F, device=dev, generator=gen)
+    y = X[:, 0] * 2 - X[:, 1] + torch.randn(n_round, device=dev, generator=gen)
+    dm = BinnedMatrix.build(X, label=y, max_bin=256)
+    per_round = {}
+    for obj, extra in (("reg:squarederror", {}),
+                       ("reg:quantileerror", {"quantile_alpha": 0.9})):
+        eng = BoostingEngine(
+            dict({"objective": obj, "max_depth": 8, "eta": 0.3,
+                  "tree_method": "gpu_hist"}, **extra), dm)
+        per_round[obj] = timeit(f"round {obj}", eng.update, reps=10)
+    print("quantile round / squarederror round: %.2f" % (
+        per_round["reg:quantileerror"] / per_round["reg:squarederror"]))
+
+
 def main():
+    if _sys.argv[1:2] == ["leaf_quantile"]:
+        return bench_leaf_quantile()
     n, F = 11_000_000, 28
     dev = torch.device("cuda")
     gen = torch.Generator(device=dev).manual_seed(0)
@@ -135,6 +197,8 @@ def main():
     )
     print(f"serving throughput: {2_000_000 / dt * 1000 / 1e6:.1f} M rows/s "
           f"(100 trees, depth 8)")
+    del Xp, out, small, dm, bins, gq, gp, hist, m
+    bench_leaf_quantile()
 
 
 if __name__ == "__main__":

@@ -9,7 +9,7 @@ pushd "$ROOT/examples" >/dev/null
 for ex in simple.py simple_predict.py simple_objectstore.py \
           train_on_parquet.py readme_sklearn_api.py explainability.py \
           simple_partitioned.py simple_tune.py simple_dask.py \
-          simple_modin.py simple_ray_dataset.py; do
+          simple_modin.py simple_ray_dataset.py quantile_interval.py; do
     echo "=== examples/$ex ==="
     python "$ex"
 done

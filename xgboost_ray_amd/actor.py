@@ -331,9 +331,7 @@ class _ActorWorker:
         if kwargs.get("output_margin"):
             pred = margin.cpu().numpy()
         else:
-            from xgboost_ray_amd.engine.objectives import get_objective
-
-            obj = get_objective(bst.objective, bst.num_class)
+            obj = bst._obj()
             pred = obj.transform_prediction(margin).cpu().numpy()
         self.dist_callbacks.after_predict(self, pred)
         return pred

@@ -255,6 +255,24 @@ class Booster:
         return int(self.params.get("num_class", 0) or 0)
 
     @property
+    def num_target(self) -> int:
+        return int(self.params.get("num_target", 1) or 1)
+
+    @property
+    def num_groups(self) -> int:
+        """Output groups: one margin column / tree per round each
+        (classes, or one per quantile alpha)."""
+        return max(1, self.num_class, self.num_target)
+
+    def _obj(self):
+        from xgboost_ray_amd.engine.objectives import get_objective
+
+        return get_objective(
+            self.objective, self.num_class,
+            quantile_alpha=self.params.get("quantile_alpha"),
+        )
+
+    @property
     def num_features(self) -> int:
         return int(self.params.get("num_feature", 0) or 0)
 
@@ -272,7 +290,7 @@ class Booster:
     def num_boosted_rounds(self) -> int:
         if self.params.get("booster") == "gblinear":
             return int(self.linear_rounds)
-        k = max(1, self.num_class) * self.num_parallel_tree
+        k = self.num_groups * self.num_parallel_tree
         return len(self.trees) // k
 
     @property
@@ -283,7 +301,7 @@ class Booster:
             if self.best_iteration is not None
             else self.num_boosted_rounds() - 1
         )
-        return (it + 1) * max(1, self.num_class) * self.num_parallel_tree
+        return (it + 1) * self.num_groups * self.num_parallel_tree
 
     def append_round(self, trees: Sequence[Tree], classes: Sequence[int]):
         self.trees.extend(trees)
@@ -342,11 +360,9 @@ class Booster:
     ) -> torch.Tensor:
         """Raw margin per row (``[n]`` or ``[n, num_class]``)."""
         from xgboost_ray_amd import ops
-        from xgboost_ray_amd.engine.objectives import get_objective
-
-        obj = get_objective(self.objective, self.num_class)
+        obj = self._obj()
         n = X.shape[0]
-        k = max(1, self.num_class)
+        k = self.num_groups
         base = obj.prob_to_margin(self.base_score)
         if self.params.get("booster") == "gblinear":
             # linear model: margin = X @ w + bias (+ base); iteration_range
@@ -409,8 +425,6 @@ class Booster:
         pred_interactions: bool = False,
         **kwargs,
     ) -> np.ndarray:
-        from xgboost_ray_amd.engine.objectives import get_objective
-
         if isinstance(data, DMatrix):
             X = data.data
             bm = data.base_margin
@@ -456,7 +470,7 @@ class Booster:
             )
         if output_margin:
             return margin.cpu().numpy()
-        obj = get_objective(self.objective, self.num_class)
+        obj = self._obj()
         return obj.transform_prediction(margin).cpu().numpy()
 
 
@@ -467,28 +481,26 @@ class Booster:
         in the cover-weighted expected value. Fully vectorized level
         walk - orders of magnitude faster than exact TreeSHAP, satisfies
         the same additivity identity contribs.sum(-1) == margin."""
-        from xgboost_ray_amd.engine.objectives import get_objective
-
         X = _as_float32_matrix(X)
         n, F = X.shape
         lo, hi = 0, self.num_boosted_rounds()
         if iteration_range is not None:
             lo, hi = iteration_range
             hi = hi or self.num_boosted_rounds()
-        obj = get_objective(self.objective, self.num_class)
+        obj = self._obj()
         base = float(obj.prob_to_margin(self.base_score))
-        k_cls = max(1, self.num_class)
+        k_cls = self.num_groups
         k = k_cls * self.num_parallel_tree
-        if self.num_class > 1:
-            out = np.zeros((n, self.num_class, F + 1), np.float64)
+        if k_cls > 1:
+            out = np.zeros((n, k_cls, F + 1), np.float64)
         else:
             out = np.zeros((n, F + 1), np.float64)
         out[..., F] += base  # global intercept joins the bias column
         rows = np.arange(n)
         for ti in range(lo * k, min(hi * k, len(self.trees))):
             t = self.trees[ti]
-            cls = self.tree_info[ti] if self.num_class > 1 else 0
-            dest = out[:, cls, :] if self.num_class > 1 else out
+            cls = self.tree_info[ti] if k_cls > 1 else 0
+            dest = out[:, cls, :] if k_cls > 1 else out
             mean_val = np.zeros(t.num_nodes, np.float64)
             cover = t.cover.astype(np.float64)
             _fill_node_means(t, mean_val, cover)
@@ -530,15 +542,13 @@ class Booster:
         if iteration_range is not None:
             lo, hi = iteration_range
             hi = hi or self.num_boosted_rounds()
-        if self.num_class > 1:
-            from xgboost_ray_amd.engine.objectives import get_objective
-
-            obj = get_objective(self.objective, self.num_class)
+        if self.num_groups > 1:
+            obj = self._obj()
             base = float(obj.prob_to_margin(self.base_score))
             outc = np.full(
-                (n, self.num_class, F + 1), 0.0, dtype=np.float64
+                (n, self.num_groups, F + 1), 0.0, dtype=np.float64
             )
-            k = max(1, self.num_class) * self.num_parallel_tree
+            k = self.num_groups * self.num_parallel_tree
             for ti in range(lo * k, min(hi * k, len(self.trees))):
                 cls = self.tree_info[ti]
                 t = self.trees[ti]
@@ -556,9 +566,7 @@ class Booster:
             self._shap_one_tree(t, X, out, scale)
         # bias column: margin expectation = sum of tree means (added in
         # _tree_shap) + the model's base margin
-        from xgboost_ray_amd.engine.objectives import get_objective
-
-        obj = get_objective(self.objective, self.num_class)
+        obj = self._obj()
         out[:, F] += float(obj.prob_to_margin(self.base_score))
         return out
 
@@ -581,7 +589,7 @@ class Booster:
         feature's SHAP value, and [F, F] is the bias - the whole matrix
         sums to the margin. Single-class models; O(F) TreeSHAP passes
         per row, so intended for explanation-sized batches."""
-        if self.num_class > 1:
+        if self.num_groups > 1:
             raise NotImplementedError(
                 "pred_interactions for multi-class models is not supported"
             )
@@ -628,7 +636,7 @@ class Booster:
         if iteration_range is not None:
             lo, hi = iteration_range
             hi = hi or self.num_boosted_rounds()
-        k = max(1, self.num_class) * self.num_parallel_tree
+        k = self.num_groups * self.num_parallel_tree
         trees = self.trees[lo * k : hi * k]
         n = X.shape[0]
         out = np.zeros((n, len(trees)), dtype=np.int32)
@@ -749,7 +757,7 @@ class Booster:
             "boost_from_average": "1",
             "num_class": str(self.num_class),
             "num_feature": str(self.num_features),
-            "num_target": "1",
+            "num_target": str(self.num_target),
         }
         trees_json = []
         for tid, t in enumerate(self.trees):
@@ -790,7 +798,7 @@ class Booster:
                 }
             )
         num_rounds = self.num_boosted_rounds()
-        k = max(1, self.num_class) * self.num_parallel_tree
+        k = self.num_groups * self.num_parallel_tree
         if self.params.get("booster") == "gblinear":
             # xgboost gblinear schema: flat weights, bias block last
             gb = {
@@ -820,7 +828,9 @@ class Booster:
                 "feature_types": [],
                 "gradient_booster": gb,
                 "learner_model_param": learner_param,
-                "objective": _objective_json(self.objective),
+                "objective": _objective_json(
+                    self.objective, self.params.get("quantile_alpha")
+                ),
             },
             "version": [2, 1, 0],
         }
@@ -839,13 +849,20 @@ class Booster:
         self.params["objective"] = learner.get("objective", {}).get(
             "name", "reg:squarederror"
         )
+        qa = learner.get("objective", {}).get(
+            "quantile_loss_param", {}
+        ).get("quantile_alpha")
+        if qa is not None:
+            self.params["quantile_alpha"] = str(qa)
+            self.params["num_target"] = int(lp.get("num_target", 1) or 1)
         self.feature_names = learner.get("feature_names") or None
         self.attributes_ = dict(learner.get("attributes", {}))
         model = learner["gradient_booster"]["model"]
         if learner["gradient_booster"].get("name") == "gblinear":
             self.params["booster"] = "gblinear"
             F = int(lp.get("num_feature", 0))
-            k = max(1, int(lp.get("num_class", 0) or 0) or 1)
+            k = max(1, int(lp.get("num_class", 0) or 0),
+                    int(self.params.get("num_target", 1) or 1))
             w = np.asarray(model["weights"], dtype=np.float64)
             self.linear_weights = w.reshape(F + 1, k)
             self.linear_rounds = int(
@@ -998,7 +1015,12 @@ def _parents_from_children(left: np.ndarray) -> np.ndarray:
     return parent
 
 
-def _objective_json(name: str) -> Dict:
+def _objective_json(name: str, quantile_alpha=None) -> Dict:
+    if name == "reg:quantileerror":
+        return {
+            "name": name,
+            "quantile_loss_param": {"quantile_alpha": str(quantile_alpha)},
+        }
     if name.startswith("binary:"):
         return {"name": name, "reg_loss_param": {"scale_pos_weight": "1"}}
     if name.startswith("multi:"):

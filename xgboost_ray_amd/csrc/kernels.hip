@@ -1168,6 +1168,93 @@ __global__ void update_margins_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// leaf_quantile_hist: one pass of the MSB-first radix select behind the
+// adaptive (exact weighted quantile) leaves of reg:quantileerror.
+//   hist[leaf][digit] += W[row]  over the leaf's rows whose order-preserving
+//   key matches prefix[leaf] in its top 8*pass bits.
+// Same segment/chunk geometry as update_margins (one chunk = one leaf), a
+// 256-bin int64 LDS histogram per chunk, non-zero bins flushed with global
+// 64-bit atomics. Integer sums only -> order-free, bitwise == CPU oracle.
+// LDS scheme: one sub-histogram per wave (4 x 2 KB) with plain per-lane
+// LDS atomics, summed at the flush. In pass 0 the digit is sign + 7
+// exponent bits, so a wave hits one or two bins; a single 2 KB histogram
+// with ballot-based pre-aggregation of equal digits measured the same
+// (the kernel is bound by the gathered resid/weight loads, not the
+// atomics), so the simpler form is kept.
+// ---------------------------------------------------------------------------
+#define LQH_THREADS PART_THREADS
+#define LQH_ROWS_PER_THREAD 8
+#define LQH_CHUNK (LQH_THREADS * LQH_ROWS_PER_THREAD)
+#define LQH_WAVES (LQH_THREADS / WAVE)
+
+__device__ __forceinline__ uint32_t lqh_key(float r) {
+  r += 0.0f;  // -0.0 folds into +0.0
+  const uint32_t u = __float_as_uint(r);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__global__ __launch_bounds__(LQH_THREADS) void leaf_quantile_hist_kernel(
+    const float* __restrict__ resid,         // [n] residuals (by row id)
+    const int64_t* __restrict__ weight,      // [n] integer weights or null
+    const int32_t* __restrict__ ridx, const int32_t* __restrict__ ridx_b,
+    const int64_t* __restrict__ node_start,  // [K] + counts at [K..2K)
+    const int64_t* __restrict__ chunk_off,   // [K+1]
+    const int64_t* __restrict__ parity,      // [K] or null
+    const int64_t* __restrict__ prefix,      // [K] top 8*pass key bits
+    long long* __restrict__ hist,            // [K,256] accumulated into
+    int K, int pass) {
+  __shared__ unsigned long long lds[LQH_WAVES * 256];
+  for (int i = threadIdx.x; i < LQH_WAVES * 256; i += LQH_THREADS)
+    lds[i] = 0ull;
+  int wg = blockIdx.x;
+  int lo = 0, hi = K;
+  while (lo + 1 < hi) {
+    int m = (lo + hi) >> 1;
+    if (chunk_off[m] <= wg) lo = m; else hi = m;
+  }
+  const int node = lo;
+  const int64_t chunk_in_node = wg - chunk_off[node];
+  const int64_t row_lo = chunk_in_node * LQH_CHUNK;
+  const int64_t count = node_start[K + node];
+  const int64_t seg_start = node_start[node];
+  if (parity != nullptr && parity[node]) ridx = ridx_b;
+  const uint32_t pfx = (uint32_t)prefix[node];
+  const int hi_shift = 32 - 8 * pass;  // bits above the digit (32 in pass 0)
+  const int lo_shift = 24 - 8 * pass;
+  __syncthreads();
+
+  int32_t rv[LQH_ROWS_PER_THREAD];
+  bool valid[LQH_ROWS_PER_THREAD];
+  #pragma unroll
+  for (int s = 0; s < LQH_ROWS_PER_THREAD; ++s) {
+    const int64_t i = row_lo + s * LQH_THREADS + threadIdx.x;
+    valid[s] = i < count;
+    rv[s] = valid[s] ? ridx[seg_start + i] : 0;
+  }
+  unsigned long long* my = lds + (threadIdx.x / WAVE) * 256;
+  #pragma unroll
+  for (int s = 0; s < LQH_ROWS_PER_THREAD; ++s) {
+    if (!valid[s]) continue;
+    const uint32_t key = lqh_key(resid[(uint32_t)rv[s]]);
+    if (pass != 0 && (key >> hi_shift) != pfx) continue;
+    // the weight is gathered only for rows that pass the prefix test
+    const unsigned long long w =
+        weight != nullptr ? (unsigned long long)weight[(uint32_t)rv[s]]
+                          : 1ull;
+    if (w != 0ull) atomicAdd(&my[(key >> lo_shift) & 255u], w);
+  }
+  __syncthreads();
+  {
+    const int b = threadIdx.x;  // LQH_THREADS == 256 bins
+    unsigned long long v = lds[b];
+    #pragma unroll
+    for (int wv = 1; wv < LQH_WAVES; ++wv) v += lds[wv * 256 + b];
+    if (v != 0ull)
+      atomicAdd((unsigned long long*)&hist[(size_t)node * 256 + b], v);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // lambdarank_grad: pairwise LambdaRank gradients, one workgroup per query
 // group; each thread owns docs i = tid, tid+256, ... and loops all other
 // docs j sequentially, so per-doc accumulation order is fixed ->
@@ -2111,6 +2198,84 @@ void update_margins(torch::Tensor margin, torch::Tensor ridx,
                      lv.data_ptr<float>(), K);
 }
 
+static_assert(LQH_THREADS == 256, "flush maps one thread to one bin");
+
+// One radix-select pass over the leaf segments; accumulates into hist
+// (int64 [K,256], device). starts/counts/parity/prefix are host tensors
+// staged through one pinned H2D.
+void leaf_quantile_hist(torch::Tensor resid, torch::Tensor weight,
+                        torch::Tensor ridx, torch::Tensor ridx_b,
+                        torch::Tensor starts, torch::Tensor counts,
+                        torch::Tensor parity, torch::Tensor prefix,
+                        int64_t pass, torch::Tensor hist) {
+  const int K = (int)starts.size(0);
+  if (K == 0) return;
+  TORCH_CHECK(on_gpu(resid) && resid.dtype() == torch::kFloat32 &&
+              resid.is_contiguous() && resid.dim() == 1);
+  TORCH_CHECK(on_gpu(ridx) && ridx.dtype() == torch::kInt32 &&
+              ridx.is_contiguous());
+  TORCH_CHECK(on_gpu(hist) && hist.dtype() == torch::kInt64 &&
+              hist.is_contiguous() && hist.numel() == (int64_t)K * 256);
+  TORCH_CHECK(pass >= 0 && pass < 4, "pass must be 0..3");
+  TORCH_CHECK(counts.size(0) == K && prefix.size(0) == K);
+  const bool have_w = weight.numel() > 0;
+  if (have_w)
+    TORCH_CHECK(on_gpu(weight) && weight.dtype() == torch::kInt64 &&
+                weight.is_contiguous() &&
+                weight.numel() == resid.numel());
+  const bool have_b = ridx_b.numel() > 0;
+  if (have_b)
+    TORCH_CHECK(on_gpu(ridx_b) && ridx_b.dtype() == torch::kInt32 &&
+                ridx_b.is_contiguous());
+  const bool have_parity = parity.numel() > 0;
+  if (have_parity)
+    TORCH_CHECK(parity.size(0) == K && have_b,
+                "parity needs the second ridx buffer");
+  auto starts_cpu = starts.to(torch::kCPU).to(torch::kInt64).contiguous();
+  auto counts_cpu = counts.to(torch::kCPU).to(torch::kInt64).contiguous();
+  auto prefix_cpu = prefix.to(torch::kCPU).to(torch::kInt64).contiguous();
+  auto parity_cpu = have_parity
+      ? parity.to(torch::kCPU).to(torch::kInt64).contiguous()
+      : torch::zeros({K}, torch::kInt64);
+  auto chunk_off_cpu = torch::zeros({K + 1}, torch::kInt64);
+  int64_t total_chunks = 0;
+  {
+    auto acc = chunk_off_cpu.accessor<int64_t, 1>();
+    auto cacc = counts_cpu.accessor<int64_t, 1>();
+    auto sacc = starts_cpu.accessor<int64_t, 1>();
+    auto pacc = parity_cpu.accessor<int64_t, 1>();
+    for (int k = 0; k < K; ++k) {
+      // every segment must lie inside the buffer it is read from
+      const int64_t lim = pacc[k] ? ridx_b.numel() : ridx.numel();
+      TORCH_CHECK(sacc[k] >= 0 && cacc[k] >= 0 && sacc[k] + cacc[k] <= lim,
+                  "leaf segment ", k, " out of range");
+      TORCH_CHECK(pacc[k] == 0 || pacc[k] == 1);
+      acc[k + 1] = acc[k] + (cacc[k] + LQH_CHUNK - 1) / LQH_CHUNK;
+    }
+    total_chunks = acc[K];
+  }
+  if (total_chunks == 0) return;
+  auto stream = c10::hip::getCurrentHIPStream();
+  static thread_local PinnedStager lqh_meta_stager;
+  auto meta_cpu = lqh_meta_stager.get(5 * K + 1);
+  cat_into_pinned(meta_cpu, {starts_cpu, counts_cpu, chunk_off_cpu,
+                             parity_cpu, prefix_cpu});
+  auto meta = meta_cpu.to(resid.device(), /*non_blocking=*/true);
+  lqh_meta_stager.mark(stream.stream());
+  int64_t* mp = meta.data_ptr<int64_t>();
+  hipLaunchKernelGGL(leaf_quantile_hist_kernel,
+                     dim3((uint32_t)total_chunks), dim3(LQH_THREADS), 0,
+                     stream.stream(), resid.data_ptr<float>(),
+                     have_w ? weight.data_ptr<int64_t>() : nullptr,
+                     ridx.data_ptr<int32_t>(),
+                     have_b ? ridx_b.data_ptr<int32_t>()
+                            : ridx.data_ptr<int32_t>(),
+                     mp, mp + 2 * K,
+                     have_parity ? mp + 3 * K + 1 : nullptr,
+                     mp + 4 * K + 1,
+                     (long long*)hist.data_ptr<int64_t>(), K, (int)pass);
+}
+
 torch::Tensor lambdarank_grad(torch::Tensor margin, torch::Tensor label,
                               torch::Tensor group_ptr, torch::Tensor rank,
                               torch::Tensor idcg, bool use_ndcg) {
@@ -2465,5 +2630,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "host wait for the depth_step pull event");
   m.def("predict_trees", &predict_trees, "tree-walk prediction");
   m.def("update_margins", &update_margins, "leaf margin update");
+  m.def("leaf_quantile_hist", &leaf_quantile_hist,
+        "per-leaf radix-select digit histogram (one pass)");
   m.def("lambdarank_grad", &lambdarank_grad, "pairwise lambdarank gradients");
 }

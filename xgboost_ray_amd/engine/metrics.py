@@ -441,6 +441,33 @@ class MPHE(Metric):
         return float(s[0] / s[1])
 
 
+class Quantile(Metric):
+    """Weighted pinball loss averaged over rows and alphas (xgboost
+    `quantile`); the alphas come from the reg:quantileerror objective."""
+
+    name = "quantile"
+    higher_better = False
+
+    def local_stats(self, margin, label, weight, qid, obj):
+        alphas = getattr(obj, "alphas", None)
+        if not alphas:
+            raise ValueError(
+                "eval_metric 'quantile' needs objective reg:quantileerror "
+                "with quantile_alpha"
+            )
+        pred = margin.double().reshape(margin.shape[0], -1)
+        a = torch.tensor(alphas, dtype=torch.float64, device=margin.device)
+        d = label.double().unsqueeze(1) - pred
+        loss = torch.where(d >= 0, a * d, (a - 1.0) * d)
+        w = _w(label, weight)
+        return torch.stack(
+            [(w.unsqueeze(1) * loss).sum() / len(alphas), w.sum()]
+        )
+
+    def finalize(self, s):
+        return float(s[0] / s[1])
+
+
 def get_metric(name: str) -> Metric:
     if name.startswith("error@"):
         return BinaryError(float(name.split("@")[1]))
@@ -467,6 +494,7 @@ def get_metric(name: str) -> Metric:
         "cox-nloglik": CoxNLogLik,
         "mphe": MPHE,
         "mape": MAPE,
+        "quantile": Quantile,
     }
     if name not in table:
         raise ValueError(f"Unsupported eval_metric: {name}")

@@ -9,7 +9,7 @@ reference's passthrough (reference test_xgboost_api.py:77-152).
 """
 
 import math
-from typing import Optional
+from typing import List, Optional
 
 import torch
 
@@ -66,6 +66,12 @@ class Objective:
     def validate_label(self, label: torch.Tensor):
         pass
 
+    def adaptive_alpha(self, output_index: int) -> Optional[float]:
+        """alpha when the trainer must re-fit this output's finished leaves
+        to the exact weighted alpha-quantile of their residuals; None (every
+        objective with a usable hessian) keeps the Newton leaves."""
+        return None
+
     def _apply_weight(self, g, h, weight):
         if weight is not None:
             g = g * weight
@@ -99,6 +105,61 @@ class AbsoluteError(Objective):
         g = torch.sign(margin - label)
         h = torch.ones_like(margin)
         return self._apply_weight(g, h, weight)
+
+
+def parse_quantile_alpha(spec) -> List[float]:
+    """``quantile_alpha`` as a float, a list/tuple, or a string such as
+    ``"[0.1,0.9]"`` -> list of floats, each strictly inside (0, 1)."""
+    if spec is None:
+        raise ValueError("reg:quantileerror needs quantile_alpha")
+    if isinstance(spec, str):
+        txt = spec.strip().strip("[]()")
+        vals = [float(x) for x in txt.split(",") if x.strip()]
+    elif isinstance(spec, (list, tuple)) or hasattr(spec, "tolist"):
+        v = spec.tolist() if hasattr(spec, "tolist") else spec
+        vals = [float(x) for x in (v if isinstance(v, (list, tuple)) else [v])]
+    else:
+        vals = [float(spec)]
+    if not vals:
+        raise ValueError("quantile_alpha is empty")
+    for a in vals:
+        if not 0.0 < a < 1.0:
+            raise ValueError(
+                f"quantile_alpha must lie strictly in (0, 1), got {a}"
+            )
+    return vals
+
+
+class QuantileError(Objective):
+    """Pinball loss; one output per alpha. The hessian is constant, so the
+    trainer re-fits every finished leaf to the exact weighted alpha-quantile
+    of its residuals (``adaptive_alpha``)."""
+
+    name = "reg:quantileerror"
+    default_metric = "quantile"
+
+    def __init__(self, quantile_alpha):
+        self.alphas = parse_quantile_alpha(quantile_alpha)
+        self.n_target = len(self.alphas)
+
+    def adaptive_alpha(self, output_index: int) -> Optional[float]:
+        return self.alphas[output_index]
+
+    def gradients(self, margin, label, weight=None, qid=None):
+        a = torch.tensor(self.alphas, dtype=margin.dtype,
+                         device=margin.device)
+        if margin.dim() == 1:
+            a = a[0]
+            y, w = label, weight
+        else:
+            y = label.unsqueeze(1)
+            w = weight.unsqueeze(1) if weight is not None else None
+        g = torch.where(margin - y >= 0, 1.0 - a, -a)
+        h = torch.ones_like(margin)
+        if w is not None:
+            g = g * w
+            h = h * w
+        return torch.stack([g, h], dim=-1)
 
 
 class Logistic(Objective):
@@ -853,11 +914,13 @@ _REGISTRY = {
 
 def get_objective(
     name_or_fn, num_class: int = 0, scale_pos_weight: float = 1.0,
-    tweedie_variance_power: float = 1.5,
+    tweedie_variance_power: float = 1.5, quantile_alpha=None,
 ) -> Objective:
     if callable(name_or_fn):
         return CustomObjective(name_or_fn, num_class)
     name = name_or_fn or "reg:squarederror"
+    if name == "reg:quantileerror":
+        return QuantileError(quantile_alpha)
     if name == "custom":
         # a model TRAINED with a custom python objective: predictions are
         # raw margins (xgboost semantics - no PredTransform is known), and

@@ -60,6 +60,7 @@ class TrainParams:
     tweedie_variance_power: float = 1.5
     aft_loss_distribution: str = "normal"
     aft_loss_distribution_scale: float = 1.0
+    quantile_alpha: object = None  # float | list | "[a,b]" (reg:quantileerror)
     tree_method: str = "hist"
     booster: str = "gbtree"
     # DART (booster="dart") dropout parameters (xgboost semantics)
@@ -247,6 +248,7 @@ class BoostingEngine:
         self.obj: Objective = get_objective(
             obj_spec, self.p.num_class, float(self.p.scale_pos_weight),
             float(self.p.tweedie_variance_power),
+            quantile_alpha=self.p.quantile_alpha,
         )
         # xgboost defaults max_delta_step to 0.7 for Poisson regression
         if (self.p.objective == "count:poisson"
@@ -257,9 +259,24 @@ class BoostingEngine:
         if isinstance(self.obj, AFT):
             self.obj.dist = str(self.p.aft_loss_distribution)
             self.obj.sigma = float(self.p.aft_loss_distribution_scale)
-        self.n_class = max(1, self.p.num_class)
+        # output groups: classes, or one per quantile alpha
+        self.n_class = max(
+            1, self.p.num_class, getattr(self.obj, "n_target", 1)
+        )
+        self._adaptive = self.obj.adaptive_alpha(0) is not None
+        self._adaptive_resid = None
+        self._int_weight_cache = None
+        if self._adaptive and self.p.monotone_constraints and any(
+            int(c) for c in self.p.monotone_constraints
+        ):
+            raise ValueError(
+                "monotone_constraints are not supported with "
+                f"{self.obj.name}: adaptive leaves ignore the weight bounds"
+            )
         if self.p.base_score is None:
-            self.p.base_score = 0.5
+            self.p.base_score = (
+                self._quantile_intercept() if self._adaptive else 0.5
+            )
         self.base_margin_const = self.obj.prob_to_margin(self.p.base_score)
 
         n = dtrain.n_rows
@@ -345,6 +362,74 @@ class BoostingEngine:
                 "booster": self.p.booster,
             }
         )
+        if self._adaptive:
+            self.booster.params["num_target"] = self.obj.n_target
+            self.booster.params["quantile_alpha"] = (
+                "[" + ",".join(repr(a) for a in self.obj.alphas) + "]"
+            )
+
+    # -- adaptive (exact weighted quantile) leaves -----------------------------
+    def _int_weights(self) -> Optional[torch.Tensor]:
+        """Integer row weights of the quantile select: None for unit
+        weights, else llrint(w * 2^30 / w_max) with the global w_max (one
+        MAX allreduce per engine, as _quantize derives its scales)."""
+        w = self.dtrain.weight
+        if w is None:
+            return None
+        if self._int_weight_cache is None:
+            mx = (w.max() if w.numel() else w.new_zeros(())).double().reshape(1)
+            if self.coll.is_distributed:
+                mx_d = mx.to(self.device) if self.device.type == "cuda" else mx
+                self.coll.allreduce_(mx_d, op="max")
+                mx = mx_d.cpu()
+            w_max = max(float(mx[0]), 1e-300)
+            self._int_weight_cache = torch.round(
+                w.double() * float(2.0 ** _QUANT_BITS) / w_max
+            ).to(torch.int64)
+        return self._int_weight_cache
+
+    def _allreduce_hook(self):
+        return self.coll.allreduce_ if self.coll.is_distributed else None
+
+    def _quantile_intercept(self) -> float:
+        """Mean over alphas of the global alpha-quantile of the labels: the
+        leaf select over one segment covering all rows, residual = label."""
+        label = self.dtrain.label
+        if label is None:
+            return 0.5
+        n = int(label.shape[0])
+        ridx = torch.arange(n, dtype=torch.int32, device=self.device)
+        resid = label.to(torch.float32).contiguous()
+        qs = []
+        for k in range(self.obj.n_target):
+            q, W = ops.leaf_quantile_select(
+                resid, self._int_weights(), ridx, [0], [n],
+                self.obj.adaptive_alpha(k), allreduce=self._allreduce_hook(),
+            )
+            qs.append(float(q[0]) if int(W[0]) > 0 else 0.5)
+        return float(np.mean(np.asarray(qs, np.float64)))
+
+    def _adaptive_leaf_values(self, cls, ridx, ridx_b, parity):
+        """Re-fit the finished leaves in _leaf_segs to eta * (exact global
+        weighted alpha-quantile of their residuals). Returns the new
+        float64 leaf values (Newton value kept where the leaf is globally
+        empty) and rewrites _leaf_segs; the caller stores them per node."""
+        segs = self._leaf_segs
+        resid = self._adaptive_resid
+        if resid.dim() == 2:
+            resid = resid[:, cls].contiguous()
+        q, W = ops.leaf_quantile_select(
+            resid, self._int_weights(), ridx,
+            [s for (s, c, v, bp) in segs], [c for (s, c, v, bp) in segs],
+            self.obj.adaptive_alpha(cls), ridx_b=ridx_b, parity=parity,
+            allreduce=self._allreduce_hook(),
+        )
+        old = np.asarray([v for (s, c, v, bp) in segs], np.float64)
+        new = np.where(W > 0, self.p.eta * q.astype(np.float64), old)
+        self._leaf_segs = [
+            (s, c, float(nv), bp) for (s, c, v, bp), nv in zip(segs, new)
+        ]
+        return new
 
     # -- resume ------------------------------------------------------------
     def load_model(self, model: Booster):
@@ -434,6 +519,11 @@ class BoostingEngine:
         gpair = self.obj.gradients(
             self.margin, label, self.dtrain.weight, self.dtrain.qid
         )
+        if self._adaptive and self.p.booster != "gblinear":
+            # residuals of the margin the gradients saw (dart dropout
+            # respected; every tree of this round fits the same ones)
+            y = label if self.margin.dim() == 1 else label.unsqueeze(1)
+            self._adaptive_resid = (y.float() - self.margin) + 0.0
         if self.p.booster == "gblinear":
             self._update_linear(gpair)
             self.iteration += 1
@@ -788,6 +878,7 @@ class BoostingEngine:
         _tick("quantize")
         self._scale_g_cur = scale_g
         self._leaf_segs = []
+        self._leaf_nids = []
         if self.p.grow_policy == "lossguide":
             return self._grow_tree_lossguide(gq, scale_g, scale_h, it, cls, ptree)
         ridx = self._sample_rows(it, cls + 101 * ptree)
@@ -1335,6 +1426,16 @@ class BoostingEngine:
                 ta, fr_nid, fr_sumg, fr_sumh, fr_start, fr_count,
                 fr_wlo, fr_whi, scale_h, parity=cur_buf,
             )
+        if self._adaptive and self._leaf_segs:
+            ta.val[np.asarray(self._leaf_nids, np.int64)] = (
+                self._adaptive_leaf_values(
+                    cls,
+                    ridx_bufs[0] if ridx_bufs is not None else ridx,
+                    ridx_bufs[1] if ridx_bufs is not None else None,
+                    [bp for (s, c, v, bp) in self._leaf_segs]
+                    if ridx_bufs is not None else None,
+                )
+            )
         # leaf margin update: every row's final node is its segment's
         # node; _finalize_leaves_soa collected (start, count, value) segs
         leaf_starts = [s for (s, c, v, bp) in self._leaf_segs]
@@ -1384,6 +1485,7 @@ class BoostingEngine:
         return tree
 
     _leaf_segs: List[Tuple[int, int, float]] = []
+    _leaf_nids: List[int] = []  # node id of each _leaf_segs entry
 
 
     def _finalize_leaves_soa(self, ta, nids, sumg, sumh, starts, counts,
@@ -1409,6 +1511,7 @@ class BoostingEngine:
         v = self.p.eta * w
         ta.val[nids] = v
         ta.cover[nids] = H
+        self._leaf_nids.extend(nids.tolist())
         self._leaf_segs.extend(
             zip(starts.tolist(), counts.tolist(), v.tolist(),
                 [parity] * int(nids.size))
@@ -1449,6 +1552,7 @@ class BoostingEngine:
             val_l[nd.nid] = vi
             cover_l[nd.nid] = Hi
             segs.append((nd.start, nd.count, vi, 0))
+            self._leaf_nids.append(nd.nid)
 
     def _finalize_leaf(self, nd: _Node, val_l, cover_l, scale_h):
         G = nd.sum_g / self._scale_g_cur
@@ -1461,6 +1565,7 @@ class BoostingEngine:
         val_l[nd.nid] = self.p.eta * w
         cover_l[nd.nid] = H
         self._leaf_segs.append((nd.start, nd.count, self.p.eta * w, 0))
+        self._leaf_nids.append(nd.nid)
 
     # -- evaluation ----------------------------------------------------------
     def eval_sets(self, evals: Sequence[EvalPack], feval=None) -> Dict[str, Dict[str, float]]:
@@ -1756,6 +1861,10 @@ class BoostingEngine:
             _, _, rec = heapq.heappop(heap)
             self._finalize_leaf_rec(rec, val_l, cover_l, scale_h)
 
+        if self._adaptive and self._leaf_segs:
+            new_vals = self._adaptive_leaf_values(cls, ridx, None, None)
+            for nid_i, nv in zip(self._leaf_nids, new_vals.tolist()):
+                val_l[nid_i] = nv
         leaf_starts = [st for (st, c, v, bp) in self._leaf_segs]
         leaf_counts = [c for (st, c, v, bp) in self._leaf_segs]
         leaf_vals = [v for (st, c, v, bp) in self._leaf_segs]
@@ -1798,6 +1907,7 @@ class BoostingEngine:
         self._leaf_segs.append(
             (rec["start"], rec["count"], self.p.eta * w, 0)
         )
+        self._leaf_nids.append(nid)
 
     # quantization scale of the current tree (set in _grow_tree via _quantize)
     _scale_g_cur: float = 1.0

@@ -206,6 +206,67 @@ def update_margins(margin, ridx, starts, counts, leaf_values,
     )
 
 
+def leaf_quantile_hist(resid, weight, ridx, starts, counts, prefix, pass_idx,
+                       out, ridx_b=None, parity=None):
+    """One MSB-first radix-select pass over leaf segments.
+
+    out[k, digit] += W[row] for the rows of segment k whose order-preserving
+    uint32 key (see ``ops.cpu.quantile_keys``) equals ``prefix[k]`` in its
+    top ``8 * pass_idx`` bits; digit = the next 8 key bits.
+    resid: f32 [n] by row id; weight: int64 [n] or None (unit weights);
+    ridx/ridx_b/starts/counts/parity: the ``update_margins`` segment
+    descriptors; prefix: int64 [L]; out: int64 [L, 256], accumulated into.
+    Integer sums: CPU and GPU agree exactly, in any row order.
+    """
+    return _impl(resid).leaf_quantile_hist(
+        resid, weight, ridx, starts, counts, prefix, pass_idx, out,
+        ridx_b=ridx_b, parity=parity,
+    )
+
+
+def leaf_quantile_select(resid, weight, ridx, starts, counts, alpha,
+                         ridx_b=None, parity=None, allreduce=None):
+    """Exact weighted lower alpha-quantile of ``resid`` in every segment.
+
+    Four ``leaf_quantile_hist`` passes; after each, ``allreduce`` (if given:
+    an in-place int64 SUM over ranks) makes the histograms global and every
+    segment keeps the first digit whose running sum reaches its remaining
+    threshold T = clamp(ceil(alpha * W_seg), 1, W_seg). int64 arithmetic
+    only. Returns (q f32 [L], W_seg int64 [L]) as numpy arrays; q is
+    meaningless where W_seg == 0.
+    """
+    import numpy as np
+
+    L = len(starts)
+    starts = torch.as_tensor(starts, dtype=torch.int64)
+    counts = torch.as_tensor(counts, dtype=torch.int64)
+    prefix = np.zeros(L, np.int64)
+    T = None
+    W_seg = None
+    for p in range(4):
+        hist = torch.zeros((L, 256), dtype=torch.int64, device=resid.device)
+        leaf_quantile_hist(resid, weight, ridx, starts, counts,
+                           torch.from_numpy(prefix), p, hist,
+                           ridx_b=ridx_b, parity=parity)
+        if allreduce is not None:
+            allreduce(hist)
+        h = hist.cpu().numpy()
+        cum = np.cumsum(h, axis=1)
+        if p == 0:
+            W_seg = cum[:, 255].copy()
+            T = np.ceil(float(alpha) * W_seg.astype(np.float64)).astype(
+                np.int64)
+            T = np.minimum(np.maximum(T, 1), W_seg)
+        digit = np.argmax(cum >= T[:, None], axis=1).astype(np.int64)
+        rows = np.arange(L)
+        T = T - (cum[rows, digit] - h[rows, digit])
+        prefix = (prefix << 8) | digit
+    key = prefix.astype(np.uint32)
+    bits = np.where(key & np.uint32(0x80000000),
+                    key ^ np.uint32(0x80000000), ~key)
+    return bits.astype(np.uint32).view(np.float32), W_seg
+
+
 def grad_fused(margin, label, weight, scale_pos_weight, mode):
     """Fused objective gradient + |g|/|h| max for the hot objectives
     (mode 0 = reg:squarederror, 1 = binary:logistic). GPU only: returns

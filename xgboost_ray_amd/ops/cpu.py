@@ -294,3 +294,34 @@ def update_margins(margin, ridx, starts, counts, leaf_values):
         if c:
             margin[ridx[s : s + c].long()] += float(leaf_values[k])
     return margin
+
+
+def quantile_keys(resid):
+    """fp32 -> order-preserving uint32 keys (held in int64): ``-0.0`` folds
+    into ``+0.0``, non-negatives get the sign bit set, negatives are
+    bit-inverted."""
+    u = (resid.float() + 0.0).contiguous().view(torch.int32).long() & 0xFFFFFFFF
+    neg = u >= 0x80000000
+    return torch.where(neg, u ^ 0xFFFFFFFF, u | 0x80000000)
+
+
+def leaf_quantile_hist(resid, weight, ridx, starts, counts, prefix, pass_idx,
+                       out, ridx_b=None, parity=None):
+    """Numerics oracle of the radix-select pass: plain torch, int64 sums."""
+    keys = quantile_keys(resid)
+    hi_shift = 32 - 8 * pass_idx
+    lo_shift = 24 - 8 * pass_idx
+    for k in range(len(starts)):
+        s, c = int(starts[k]), int(counts[k])
+        if not c:
+            continue
+        src = ridx_b if (parity is not None and int(parity[k])) else ridx
+        rows = src[s : s + c].long()
+        kk = keys[rows]
+        w = (weight[rows] if weight is not None
+             else torch.ones(c, dtype=torch.int64))
+        if pass_idx:
+            m = (kk >> hi_shift) == int(prefix[k])
+            kk, w = kk[m], w[m]
+        out[k].index_add_(0, (kk >> lo_shift) & 255, w)
+    return out

@@ -186,6 +186,28 @@ def update_margins(margin, ridx, starts, counts, leaf_values,
     return margin
 
 
+def leaf_quantile_hist(resid, weight, ridx, starts, counts, prefix, pass_idx,
+                       out, ridx_b=None, parity=None):
+    # starts/counts/parity/prefix stay on the HOST (one pinned H2D, as in
+    # update_margins).
+    dev = resid.device
+    w = weight if weight is not None else torch.zeros(
+        0, dtype=torch.int64, device=dev)
+    rb = ridx_b if ridx_b is not None else torch.zeros(
+        0, dtype=torch.int32, device=dev)
+    par = (torch.as_tensor(parity, dtype=torch.int64)
+           if parity is not None and ridx_b is not None
+           else torch.zeros(0, dtype=torch.int64))
+    _load().leaf_quantile_hist(
+        resid, w, ridx, rb,
+        torch.as_tensor(starts, dtype=torch.int64),
+        torch.as_tensor(counts, dtype=torch.int64),
+        par, torch.as_tensor(prefix, dtype=torch.int64),
+        int(pass_idx), out,
+    )
+    return out
+
+
 def grad_fused(margin, label, weight, scale_pos_weight, mode):
     w = weight if weight is not None else torch.zeros(
         0, dtype=torch.float32, device=margin.device)

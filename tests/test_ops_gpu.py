@@ -488,9 +488,9 @@ def test_predict_lds_matches_plain():
 
 
 def test_one_sync_path_bitwise():
-    """Opt-in single-sync depth loop (RXGB_ONE_SYNC=1) vs the default
-    2-sync path: identical models (the device plan kernel's split
-    predicate must replay exactly on the host)."""
+    """Default single-sync depth loop (RXGB_ONE_SYNC=1) vs the 2-sync
+    path that RXGB_ONE_SYNC=0 restores: identical models (the device
+    plan kernel's split predicate must replay exactly on the host)."""
     import os
 
     from xgboost_ray_amd.engine.quantile import BinnedMatrix

@@ -92,9 +92,84 @@ def bench_leaf_quantile(n=11_000_000, K=256, F=28, n_round=2_000_000):
         per_round["reg:quantileerror"] / per_round["reg:squarederror"]))
 
 
+def bench_tree_shap(n=1_000_000, F=28, rounds=100, depth=8,
+                    n_inter=65_536, n_host=64):
+    """Path-form TreeSHAP: contributions of n rows and interactions of
+    n_inter rows through ``rounds`` trees of depth ``depth``, against
+    predict_trees on the same input and against the host recursion
+    (``booster._tree_shap``) on n_host of the rows."""
+    from xgboost_ray_amd.engine.trainer import BoostingEngine
+
+    dev = torch.device("cuda")
+    gen = torch.Generator(device=dev).manual_seed(0)
+    X = torch.randn(n, F, device=dev, generator=gen)
+    y = (X[:, 0] * X[:, 1] + X[:, 2:6].sum(1)
+         + torch.randn(n, device=dev, generator=gen))
+    eng = BoostingEngine(
+        {"objective": "reg:squarederror", "max_depth": depth, "eta": 0.3,
+         "tree_method": "gpu_hist"},
+        BinnedMatrix.build(X, label=y, max_bin=256))
+    for _ in range(rounds):
+        eng.update()
+    bst = eng.booster
+    paths = ops.cpu.shap_paths(bst.trees, 1.0)
+    lens = np.diff(paths["path_ptr"]).astype(np.int64)
+    print(f"forest: {len(bst.trees)} trees, {len(lens)} paths, "
+          f"{int(lens.sum())} elements, longest path {paths['max_len']}")
+    # nominal float64 operations per row, a division counted as one:
+    # EXTEND 8 per inner step (m(m+1)/2 steps), unwound_sum 7 per step on
+    # a followed element (m steps for each of the m elements)
+    print(f"inner steps per row: EXTEND {int((lens * (lens + 1) // 2).sum())}"
+          f", unwound_sum {int((lens * lens).sum())}")
+    flop_c = float((8 * lens * (lens + 1) // 2 + 7 * lens * lens).sum())
+    flop_i = float((8 * lens * (lens + 1) // 2 + 7 * lens * lens
+                    + 7 * lens * (lens - 1) * (lens - 1)).sum())
+
+    flat = bst._flat_trees(dev)
+    margin = torch.zeros(n, device=dev)
+    t_pred = timeit("predict_trees", lambda: ops.predict_trees(
+        X, flat["feat"], flat["thr"], flat["left"], flat["default_left"],
+        flat["value"], flat["tree_ptr"], margin))
+
+    out = torch.zeros((n, 1, F + 1), dtype=torch.float64, device=dev)
+    t_c = timeit("tree_shap", lambda: ops.tree_shap(X, paths, 1, out),
+                 reps=3)
+    print(f"  contribs: {n / t_c / 1e3:8.3f} M rows/s, "
+          f"{flop_c * n / t_c / 1e9:6.2f} TFLOP/s float64 nominal "
+          f"({100 * flop_c * n / t_c / 1e9 / 78.6:.1f} % of the 78.6 TF "
+          f"vector peak), {t_c / t_pred:.0f} x predict_trees")
+    Xi = X[:n_inter].contiguous()
+    out_i = torch.zeros((n_inter, F + 1, F + 1), dtype=torch.float64,
+                        device=dev)
+    t_i = timeit(f"interactions n={n_inter}",
+                 lambda: ops.tree_shap_interactions(Xi, paths, out_i),
+                 reps=3)
+    print(f"  interactions: {n_inter / t_i / 1e3:8.3f} M rows/s, "
+          f"{flop_i * n_inter / t_i / 1e9:6.2f} TFLOP/s float64 nominal, "
+          f"{t_i / n_inter / (t_pred / n):.0f} x predict_trees per row")
+
+    # the public route at the threshold batch, host copies included
+    Xh = X[:16384].cpu().numpy()
+    t0 = time.perf_counter()
+    bst.predict(Xh, pred_contribs=True)
+    t_route = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    bst.predict(Xh[:n_host], pred_contribs=True)  # small batch: recursion
+    t_host = time.perf_counter() - t0
+    print(f"  Booster.predict(pred_contribs) 16384 rows on the device: "
+          f"{t_route:.3f} s ({16384 / t_route:.0f} rows/s, paths built "
+          f"in this call)")
+    print(f"  host recursion, {n_host} rows: {t_host:.2f} s "
+          f"({n_host / t_host:.1f} rows/s) -> 16384 rows would take "
+          f"{t_host / n_host * 16384:.0f} s, "
+          f"{t_host / n_host * 16384 / t_route:.0f} x the device route")
+
+
 def main():
     if _sys.argv[1:2] == ["leaf_quantile"]:
         return bench_leaf_quantile()
+    if _sys.argv[1:2] == ["tree_shap"]:
+        return bench_tree_shap()
     n, F = 11_000_000, 28
     dev = torch.device("cuda")
     gen = torch.Generator(device=dev).manual_seed(0)

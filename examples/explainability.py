@@ -44,6 +44,13 @@ def main():
           np.unravel_index(np.abs(inter[0, :5, :5]
                                   - np.diag(np.diag(inter[0, :5, :5])))
                            .argmax(), (5, 5)))
+    import torch
+
+    if torch.cuda.is_available():
+        # >= 16384 rows: exact TreeSHAP of the whole matrix on the GPU
+        # (the path-form HIP kernel; RXGB_SHAP_GPU=0 keeps it on the CPU)
+        mean_abs = np.abs(bst.predict(X, pred_contribs=True)[:, :5]).mean(0)
+        print("mean |SHAP| over all rows:", np.round(mean_abs, 3))
     leaves = bst.predict(rows, pred_leaf=True)
     print("leaf ids (row 0):", leaves[0][:8])
 

@@ -283,7 +283,11 @@ class _ActorWorker:
             raise RuntimeError(f"Prediction data {data_uid} not loaded")
         it_range = kwargs.get("iteration_range")
         if kwargs.get("pred_leaf") or kwargs.get("pred_contribs"):
-            # leaf-index / SHAP modes run per shard on the CPU tree walk
+            # leaf-index / SHAP modes run per shard through Booster.predict:
+            # pred_leaf is the CPU tree walk; pred_contribs shards of
+            # >= 16384 rows run the path-form TreeSHAP kernel on this
+            # actor's GPU (smaller ones, or RXGB_SHAP_GPU=0, the CPU
+            # recursion)
             if shard.get("streaming"):
                 parts = [
                     bst.predict(chunk["data"], **kwargs)

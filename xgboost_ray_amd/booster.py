@@ -9,6 +9,7 @@ XGBoost JSON model schema so models interoperate with stock XGBoost
 """
 
 import json
+import os
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Union
 
@@ -223,6 +224,12 @@ def _tree_shap(t, x, mean_val, cover, out, scale, condition=0,
     recurse(0, [], 1.0, 1.0, -1, 1.0)
 
 
+# pred_contribs / pred_interactions batches of at least this many rows run
+# the path-form TreeSHAP kernel when a GPU is present (the bulk-prediction
+# rule of Booster.predict); RXGB_SHAP_GPU=0 keeps them on the recursion
+SHAP_GPU_MIN_ROWS = 16384
+
+
 class Booster:
     def __init__(
         self,
@@ -244,6 +251,7 @@ class Booster:
         self.linear_weights = None
         self.linear_rounds = 0
         self._flat_cache = None
+        self._shap_cache = None
 
     # -- core info ---------------------------------------------------------
     @property
@@ -307,6 +315,7 @@ class Booster:
         self.trees.extend(trees)
         self.tree_info.extend(int(c) for c in classes)
         self._flat_cache = None
+        self._shap_cache = None
 
     # -- attributes (xgboost API parity) -----------------------------------
     def attr(self, key):
@@ -542,6 +551,9 @@ class Booster:
         if iteration_range is not None:
             lo, hi = iteration_range
             hi = hi or self.num_boosted_rounds()
+        paths = self._shap_device_paths(n, F, lo, hi)
+        if paths is not None:
+            return self._predict_contribs_device(X, paths)
         if self.num_groups > 1:
             obj = self._obj()
             base = float(obj.prob_to_margin(self.base_score))
@@ -570,6 +582,50 @@ class Booster:
         out[:, F] += float(obj.prob_to_margin(self.base_score))
         return out
 
+
+    def _shap_device_paths(self, n, F, lo, hi):
+        """Path form of rounds [lo, hi) when this batch takes the device
+        route, else None: fewer than SHAP_GPU_MIN_ROWS rows, no GPU,
+        RXGB_SHAP_GPU=0, or a forest the path-form op does not take (a
+        root-to-leaf path with more than ops.SHAP_MAX_PATH_LEN unique
+        features, or a split beyond X's columns) - those run the CPU
+        recursion, as over-tile trees fall back in predict_trees."""
+        if (
+            n < SHAP_GPU_MIN_ROWS
+            or os.environ.get("RXGB_SHAP_GPU") == "0"
+            or not torch.cuda.is_available()
+        ):
+            return None
+        from xgboost_ray_amd import ops
+
+        cache = getattr(self, "_shap_cache", None)
+        if cache is None or cache[0] != (lo, hi):
+            k = self.num_groups * self.num_parallel_tree
+            idx = range(lo * k, min(hi * k, len(self.trees)))
+            scale = (1.0 / self.num_parallel_tree
+                     if self.num_parallel_tree > 1 else 1.0)
+            paths = ops.cpu.shap_paths(
+                [self.trees[i] for i in idx], scale,
+                [self.tree_info[i] if self.num_groups > 1 else 0
+                 for i in idx],
+            )
+            cache = self._shap_cache = ((lo, hi), paths)
+        paths = cache[1]
+        if paths["max_len"] > ops.SHAP_MAX_PATH_LEN or paths["n_features"] > F:
+            return None
+        return paths
+
+    def _predict_contribs_device(self, X, paths):
+        from xgboost_ray_amd import ops
+
+        n, F = X.shape
+        G = self.num_groups
+        out = torch.zeros((n, G, F + 1), dtype=torch.float64)
+        ops.tree_shap(torch.from_numpy(X).cuda(), paths, G, out)
+        out = out.numpy()
+        out[:, : paths["n_groups"], F] += paths["bias"][None, :]
+        out[:, :, F] += float(self._obj().prob_to_margin(self.base_score))
+        return out if G > 1 else out[:, 0, :]
 
     @staticmethod
     def _shap_one_tree(t, X, out, scale):
@@ -604,9 +660,17 @@ class Booster:
         trees = self.trees[lo * k : hi * k]
         scale = 1.0 / k if k > 1 else 1.0
         M = np.zeros((n, F + 1, F + 1), dtype=np.float64)
+        paths = self._shap_device_paths(n, F, lo, hi)
+        if paths is not None:
+            from xgboost_ray_amd import ops
+
+            # raw off-diagonal terms from the kernel; the symmetrisation
+            # and diagonals below are shared with the recursion
+            ops.tree_shap_interactions(
+                torch.from_numpy(X).cuda(), paths, torch.from_numpy(M))
         on = np.zeros((n, F + 1), dtype=np.float64)
         off = np.zeros((n, F + 1), dtype=np.float64)
-        for i in range(F):
+        for i in range(F if paths is None else 0):
             on[:] = 0.0
             off[:] = 0.0
             for t in trees:
@@ -664,6 +728,7 @@ class Booster:
     def __getstate__(self):
         state = self.__dict__.copy()
         state["_flat_cache"] = None
+        state["_shap_cache"] = None
         return state
 
     def __setstate__(self, state):
@@ -871,6 +936,7 @@ class Booster:
             self.trees = []
             self.tree_info = []
             self._flat_cache = None
+            self._shap_cache = None
             return
         gbm_param = model.get("gbtree_model_param", {})
         if "num_parallel_tree" in gbm_param:
@@ -903,6 +969,7 @@ class Booster:
         if not self.tree_info:
             self.tree_info = [0] * len(self.trees)
         self._flat_cache = None
+        self._shap_cache = None
 
     def get_score(self, fmap: str = "", importance_type: str = "weight"):
         """Per-feature importance (xgboost Booster.get_score parity).

@@ -13,6 +13,8 @@
 //     two-phase begin/finish entry, device-planned variant)
 //   - grad_fused:     fused objective gradient + |g|/|h| block maxes
 //   - predict_trees:  packed-node tree walk (LDS tree-tiled serving path)
+//   - tree_shap:      exact TreeSHAP contributions / interactions in path
+//     form, float64, one row per thread (no atomics)
 //
 // Design notes (per /opt/skills/guides/cdna_hip_programming.md):
 //   wave = 64 lanes; LDS = 160 KiB/CU; histogram tiles sized so 1-2
@@ -2148,6 +2150,277 @@ void predict_trees(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
                      out.data_ptr<float>(), (float)tree_weight, n, F, T);
 }
 
+// ---------------------------------------------------------------------------
+// tree_shap: exact TreeSHAP in path form (one root-to-leaf path = one
+// independent unit, one element per unique feature; host side:
+// ops.cpu.shap_paths). One thread owns one row and walks every path in
+// order, so a row's output is written by that thread alone in a fixed
+// sequence: no float atomics, bitwise repeatable. All arithmetic is
+// float64 in the operation order of ops.cpu.tree_shap (the build keeps
+// FMA contraction off).
+//
+// LDS (dynamic): path elements are staged in tiles of SHAP_TILE_ELEMS,
+// as predict_trees_lds stages nodes - every row of the block reads the
+// same element, a broadcast. The per-row permutation-weight vector is an
+// LDS column laid out [element][thread]: a wave's 64 accesses are 64
+// consecutive 8-byte words, conflict-free, and nothing is runtime-indexed
+// in registers (no scratch). INTER adds a second column for the weights
+// of the path with one element unwound.
+// ---------------------------------------------------------------------------
+#define SHAP_TILE_ELEMS 1024
+#define SHAP_MAX_PATH_LEN 32
+#define SHAP_THREADS 128
+#define SHAP_INTER_THREADS 64
+
+#define SHAP_RCP_LEN (SHAP_MAX_PATH_LEN + 8)
+
+// a / k for a small positive integer k, given r = RN(1 / k) (the LDS table
+// every block fills with true divisions): q = RN(a r), one exact FMA
+// remainder, one FMA correction (Markstein's sequence) - the IEEE
+// quotient in 3 instructions instead of the ~14 of the generic
+// expansion. The divisions by path positions (ln, ln + 1, j + 1) are the
+// bulk of the kernel's instruction stream; the ones by a zero_fraction
+// stay generic.
+__device__ __forceinline__ double shap_div_int(double a, int k,
+                                               const double* rcp) {
+  const double r = rcp[k];
+  const double q = a * r;
+  return fma(fma(-q, (double)k, a), r, q);
+}
+
+// _tree_shap's unwind_sum over weights w[0..ln] (column stride bs)
+__device__ __forceinline__ double shap_unwound_sum(
+    const double* w, int bs, int ln, double pz, bool hot,
+    const double* rcp) {
+  double total = 0.0;
+  if (hot) {
+    double nxt = w[ln * bs];
+    for (int j = ln - 1; j >= 0; --j) {
+      const double tmp = shap_div_int(nxt * (double)(ln + 1), j + 1, rcp);
+      total += tmp;
+      nxt = w[j * bs] -
+            shap_div_int(tmp * pz * (double)(ln - j), ln + 1, rcp);
+    }
+  } else {
+    for (int j = 0; j < ln; ++j)
+      total += w[j * bs] * (double)(ln + 1) / (pz * (double)(ln - j));
+  }
+  return total;
+}
+
+template <bool INTER>
+__global__ void tree_shap_kernel(
+    const float* __restrict__ X,
+    const int4* __restrict__ elem,      // {feature | miss_ok << 31, lo, hi, 0}
+    const double* __restrict__ elem_z,  // zero_fraction
+    const int32_t* __restrict__ path_ptr, const double* __restrict__ path_val,
+    const int32_t* __restrict__ path_grp,
+    const int32_t* __restrict__ tile_ptr,  // [n_tiles+1] path indices
+    int n_tiles, double* __restrict__ out, int64_t n, int F, int G,
+    int wlen) {  // wlen = longest path + 1 weights per row
+  extern __shared__ __align__(16) double shap_lds[];
+  double* lds_z = shap_lds;
+  int4* lds_e = (int4*)(shap_lds + SHAP_TILE_ELEMS);
+  double* rcp = shap_lds + 3 * SHAP_TILE_ELEMS;  // rcp[k] = 1 / k
+  const int bs = (int)blockDim.x;
+  double* w = rcp + SHAP_RCP_LEN + threadIdx.x;
+  double* w2 = w + (size_t)wlen * bs;  // INTER only
+  if (threadIdx.x < SHAP_RCP_LEN)  // published by the first tile's barrier
+    rcp[threadIdx.x] = 1.0 / (double)(threadIdx.x ? threadIdx.x : 1);
+  const int64_t row_stride =
+      INTER ? (int64_t)(F + 1) * (F + 1) : (int64_t)G * (F + 1);
+  const int64_t n_blocks = (n + bs - 1) / bs;
+  for (int64_t rb = blockIdx.x; rb < n_blocks; rb += gridDim.x) {
+    const int64_t row = rb * bs + threadIdx.x;
+    const bool active = row < n;
+    const float* xr = X + (active ? row : 0) * (int64_t)F;
+    double* orow = out + (active ? row : 0) * row_stride;
+    for (int tile = 0; tile < n_tiles; ++tile) {
+      const int p0 = tile_ptr[tile], p1 = tile_ptr[tile + 1];
+      const int eb = path_ptr[p0];
+      const int span = path_ptr[p1] - eb;
+      __syncthreads();  // previous tile's walk done before overwriting
+      for (int i = threadIdx.x; i < span; i += bs) {
+        lds_e[i] = elem[eb + i];
+        lds_z[i] = elem_z[eb + i];
+      }
+      __syncthreads();
+      if (!active) continue;
+      for (int p = p0; p < p1; ++p) {
+        const int e0 = path_ptr[p] - eb;
+        const int m = path_ptr[p + 1] - path_ptr[p];
+        if (m == 0 || (INTER && m < 2)) continue;
+        // one_fraction of every element, as a bit mask
+        uint32_t omask = 0;
+        bool dead = false;
+        for (int i = 0; i < m; ++i) {
+          const int4 e = lds_e[e0 + i];
+          const float x = xr[e.x & 0x7FFFFFFF];
+          const float lo = __int_as_float(e.y), hi = __int_as_float(e.z);
+          const bool o = isnan(x) ? (e.x < 0)
+                                  : (x >= lo && (x < hi || hi == INFINITY));
+          omask |= (uint32_t)o << i;
+          // one == 0 and zero == 0: every subset term vanishes
+          dead |= (!o && lds_z[e0 + i] == 0.0);
+        }
+        if (dead) continue;
+        const double v = path_val[p];
+        // EXTEND over the dummy root element, then every element
+        w[0] = 1.0;
+        for (int k = 1; k <= m; ++k) {
+          const double pz = lds_z[e0 + k - 1];
+          const double po = (omask >> (k - 1)) & 1u ? 1.0 : 0.0;
+          double carry = 0.0;
+          for (int i = k - 1; i >= 0; --i) {
+            const double wi = w[i * bs];
+            w[(i + 1) * bs] =
+                carry + shap_div_int(po * wi * (double)(i + 1), k + 1, rcp);
+            carry = shap_div_int(pz * wi * (double)(k - i), k + 1, rcp);
+          }
+          w[0] = carry;
+        }
+        if (!INTER) {
+          double* dest = orow + (int64_t)path_grp[p] * (F + 1);
+          for (int i = 0; i < m; ++i) {
+            const double pz = lds_z[e0 + i];
+            const bool hot = (omask >> i) & 1u;
+            const double s = shap_unwound_sum(w, bs, m, pz, hot, rcp);
+            dest[lds_e[e0 + i].x & 0x7FFFFFFF] +=
+                s * ((hot ? 1.0 : 0.0) - pz) * v;
+          }
+        } else {
+          for (int c = 0; c < m; ++c) {
+            const double pzc = lds_z[e0 + c];
+            const bool hotc = (omask >> c) & 1u;
+            // UNWIND element c: w2[0..m-1] are the weights of E \ {c}
+            if (hotc) {
+              double nxt = w[m * bs];
+              for (int j = m - 1; j >= 0; --j) {
+                const double tmp =
+                    shap_div_int(nxt * (double)(m + 1), j + 1, rcp);
+                nxt = w[j * bs] -
+                      shap_div_int(tmp * pzc * (double)(m - j), m + 1, rcp);
+                w2[j * bs] = tmp;
+              }
+            } else {
+              for (int j = 0; j < m; ++j)
+                w2[j * bs] =
+                    w[j * bs] * (double)(m + 1) / (pzc * (double)(m - j));
+            }
+            const double half = ((hotc ? 1.0 : 0.0) - pzc) / 2.0;
+            double* dest =
+                orow + (int64_t)(lds_e[e0 + c].x & 0x7FFFFFFF) * (F + 1);
+            for (int j = 0; j < m; ++j) {
+              if (j == c) continue;
+              const double pz = lds_z[e0 + j];
+              const bool hot = (omask >> j) & 1u;
+              const double s = shap_unwound_sum(w2, bs, m - 1, pz, hot, rcp);
+              dest[lds_e[e0 + j].x & 0x7FFFFFFF] +=
+                  half * s * ((hot ? 1.0 : 0.0) - pz) * v;
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
+// path_ptr arrives on the HOST: the tiling (consecutive paths whose
+// elements fit SHAP_TILE_ELEMS) is a scan over it, and every index the
+// kernel forms from it is checked here before anything is launched.
+void tree_shap(torch::Tensor X, torch::Tensor elem, torch::Tensor elem_z,
+               torch::Tensor path_ptr, torch::Tensor path_val,
+               torch::Tensor path_grp, torch::Tensor out, int64_t n_groups,
+               bool interactions) {
+  TORCH_CHECK(on_gpu(X) && on_gpu(elem) && on_gpu(elem_z) &&
+              on_gpu(path_val) && on_gpu(path_grp) && on_gpu(out),
+              "tree_shap: tensors must be on the GPU");
+  TORCH_CHECK(!on_gpu(path_ptr) && path_ptr.scalar_type() == torch::kInt32 &&
+              path_ptr.dim() == 1 && path_ptr.size(0) >= 1 &&
+              path_ptr.is_contiguous(),
+              "tree_shap: path_ptr must be a host int32 vector");
+  TORCH_CHECK(X.scalar_type() == torch::kFloat32 && X.dim() == 2 &&
+              X.is_contiguous(), "tree_shap: X must be contiguous f32 [n, F]");
+  TORCH_CHECK(out.scalar_type() == torch::kFloat64 && out.is_contiguous(),
+              "tree_shap: out must be contiguous f64");
+  TORCH_CHECK(elem.scalar_type() == torch::kInt32 && elem.dim() == 2 &&
+              elem.size(1) == 4 && elem.is_contiguous() &&
+              elem_z.scalar_type() == torch::kFloat64 &&
+              elem_z.is_contiguous() &&
+              path_val.scalar_type() == torch::kFloat64 &&
+              path_val.is_contiguous() &&
+              path_grp.scalar_type() == torch::kInt32 &&
+              path_grp.is_contiguous(), "tree_shap: bad path arrays");
+  const int64_t n = X.size(0);
+  const int F = (int)X.size(1);
+  const int64_t P = path_ptr.size(0) - 1;
+  const int G = interactions ? 1 : (int)n_groups;
+  TORCH_CHECK(G >= 1, "tree_shap: n_groups must be >= 1");
+  const int64_t per_row =
+      interactions ? (int64_t)(F + 1) * (F + 1) : (int64_t)G * (F + 1);
+  TORCH_CHECK(out.numel() == n * per_row, "tree_shap: out has ",
+              out.numel(), " elements, expected ", n * per_row);
+  TORCH_CHECK(path_val.numel() == P && path_grp.numel() == P,
+              "tree_shap: per-path arrays do not match path_ptr");
+  const int32_t* pp = path_ptr.data_ptr<int32_t>();
+  TORCH_CHECK(pp[0] == 0 && pp[P] == elem.size(0) &&
+              elem_z.numel() == elem.size(0),
+              "tree_shap: path_ptr does not span the element arrays");
+  if (n == 0 || P == 0) return;
+  std::vector<int32_t> tiles;
+  tiles.push_back(0);
+  int max_len = 0;
+  int64_t tile_e0 = 0;
+  for (int64_t p = 0; p < P; ++p) {
+    const int len = pp[p + 1] - pp[p];
+    TORCH_CHECK(len >= 0 && len <= SHAP_MAX_PATH_LEN, "tree_shap: path ", p,
+                " has ", len, " elements (max ", SHAP_MAX_PATH_LEN, ")");
+    if (len > max_len) max_len = len;
+    if (pp[p + 1] - tile_e0 > SHAP_TILE_ELEMS) {  // close the tile before p
+      tiles.push_back((int32_t)p);
+      tile_e0 = pp[p];
+    }
+  }
+  tiles.push_back((int32_t)P);
+  auto dev_i32 = [&](const int32_t* src, int64_t len) {
+    return torch::from_blob(const_cast<int32_t*>(src), {len},
+                            torch::TensorOptions().dtype(torch::kInt32))
+        .clone().to(X.device());
+  };
+  auto ptr_d = dev_i32(pp, P + 1);
+  auto tile_d = dev_i32(tiles.data(), (int64_t)tiles.size());
+  const int threads = interactions ? SHAP_INTER_THREADS : SHAP_THREADS;
+  const int wlen = max_len + 1;
+  const size_t lds_bytes =
+      (size_t)SHAP_TILE_ELEMS * 24 + SHAP_RCP_LEN * sizeof(double) +
+      (size_t)wlen * threads * sizeof(double) * (interactions ? 2 : 1);
+  TORCH_CHECK(lds_bytes <= 64 * 1024, "tree_shap: LDS budget exceeded");
+  const int64_t blocks = std::min<int64_t>(ceil_div(n, threads), 65536);
+  auto stream = c10::hip::getCurrentHIPStream();
+  if (interactions) {
+    hipLaunchKernelGGL((tree_shap_kernel<true>), dim3((uint32_t)blocks),
+                       dim3(threads), lds_bytes, stream.stream(),
+                       X.data_ptr<float>(),
+                       (const int4*)elem.data_ptr<int32_t>(),
+                       elem_z.data_ptr<double>(), ptr_d.data_ptr<int32_t>(),
+                       path_val.data_ptr<double>(),
+                       path_grp.data_ptr<int32_t>(),
+                       tile_d.data_ptr<int32_t>(), (int)tiles.size() - 1,
+                       out.data_ptr<double>(), n, F, G, wlen);
+  } else {
+    hipLaunchKernelGGL((tree_shap_kernel<false>), dim3((uint32_t)blocks),
+                       dim3(threads), lds_bytes, stream.stream(),
+                       X.data_ptr<float>(),
+                       (const int4*)elem.data_ptr<int32_t>(),
+                       elem_z.data_ptr<double>(), ptr_d.data_ptr<int32_t>(),
+                       path_val.data_ptr<double>(),
+                       path_grp.data_ptr<int32_t>(),
+                       tile_d.data_ptr<int32_t>(), (int)tiles.size() - 1,
+                       out.data_ptr<double>(), n, F, G, wlen);
+  }
+  CHECK_HIP(hipGetLastError());
+}
+
 void update_margins(torch::Tensor margin, torch::Tensor ridx,
                     torch::Tensor starts, torch::Tensor counts,
                     torch::Tensor leaf_vals, torch::Tensor ridx_b,
@@ -2629,6 +2902,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wait_pull_event", &wait_pull_event,
         "host wait for the depth_step pull event");
   m.def("predict_trees", &predict_trees, "tree-walk prediction");
+  m.def("tree_shap", &tree_shap,
+        "path-form exact TreeSHAP (contributions or interactions)");
+  m.attr("SHAP_TILE_ELEMS") = SHAP_TILE_ELEMS;
+  m.attr("SHAP_MAX_PATH_LEN") = SHAP_MAX_PATH_LEN;
   m.def("update_margins", &update_margins, "leaf margin update");
   m.def("leaf_quantile_hist", &leaf_quantile_hist,
         "per-leaf radix-select digit histogram (one pass)");

@@ -188,6 +188,47 @@ def predict_trees(
     )
 
 
+SHAP_MAX_PATH_LEN = _cpu.SHAP_MAX_PATH_LEN
+
+
+def tree_shap(X, paths, n_groups, out, **kw):
+    """Exact TreeSHAP feature contributions in path form.
+
+    X: fp32 [n, F] row-major raw features (NaN = missing). paths: the
+    dict ``ops.cpu.shap_paths`` builds from a forest (one path per leaf,
+    one element per unique feature; longest path <= SHAP_MAX_PATH_LEN,
+    else ValueError - callers fall back to the recursion). out: float64
+    [n, n_groups, F+1] tensor, ACCUMULATED into: for every element i of
+    every path, out[row, group, feature_i] +=
+    unwound_sum(path, i) * (one_i - zero_i) * value. Only feature columns
+    are written; the bias column (``paths["bias"]`` + base margin) is the
+    caller's. All arithmetic is float64 and each row's sums run in path
+    order, so the result is bitwise repeatable.
+
+    Dispatches on X's device. On the GPU ``out`` may live on the host:
+    rows are processed in chunks whose device output stays under
+    ``max_out_bytes`` (keyword, default ``ops.gpu.SHAP_OUT_BYTES``), each
+    chunk copied out before the next one runs.
+    """
+    return _impl(X).tree_shap(X, paths, n_groups, out, **kw)
+
+
+def tree_shap_interactions(X, paths, out, **kw):
+    """Raw off-diagonal SHAP interaction terms in path form.
+
+    X, paths as in ``tree_shap`` (single output group). out: float64
+    [n, F+1, F+1] tensor, ACCUMULATED into: for a path with elements E,
+    every c in E and j in E \\ {c} adds
+    (one_c - zero_c) / 2 * unwound_sum(E \\ {c}, j) * (one_j - zero_j) * value
+    to out[row, feature_c, feature_j]. The diagonal, the bias row/column
+    and the (M + M^T) / 2 symmetrisation are the caller's
+    (``Booster.predict_interactions``). Same dispatch, chunking
+    (``max_out_bytes``, default ``ops.gpu.SHAP_INTER_OUT_BYTES``) and
+    repeatability as ``tree_shap``.
+    """
+    return _impl(X).tree_shap_interactions(X, paths, out, **kw)
+
+
 def update_margins(margin, ridx, starts, counts, leaf_values,
                    ridx_b=None, parity=None):
     """margin[ridx[seg_k]] += leaf_values[k] for each final-leaf segment.

@@ -325,3 +325,257 @@ def leaf_quantile_hist(resid, weight, ridx, starts, counts, prefix, pass_idx,
             kk, w = kk[m], w[m]
         out[k].index_add_(0, (kk >> lo_shift) & 255, w)
     return out
+
+
+# ---------------------------------------------------------------------------
+# Exact TreeSHAP in path form
+# ---------------------------------------------------------------------------
+# longest root-to-leaf path, counted in UNIQUE features, the path-form ops
+# accept (the HIP kernel sizes its per-row weight column by it)
+SHAP_MAX_PATH_LEN = 32
+
+
+def _as_numpy(a):
+    return a.detach().numpy() if isinstance(a, torch.Tensor) else a
+
+
+def shap_paths(trees, scales=1.0, groups=None):
+    """Flatten a forest into independent root-to-leaf paths (the
+    GPUTreeShap formulation of Lundberg's TreeSHAP).
+
+    One path per leaf, one ELEMENT per unique feature on it. Repeated
+    splits on a feature merge into one element carrying
+
+    - ``feature``        int32
+    - ``lo``, ``hi``     float32 half-open interval of thresholds, from
+      (-inf, +inf): going left at ``thr`` sets hi = min(hi, thr), going
+      right sets lo = max(lo, thr). ``hi == +inf`` means "no upper bound"
+      (a row value of +inf takes every right branch, so it lies inside)
+    - ``miss_ok``        uint8, AND over the merged splits of "default
+      direction == direction taken"
+    - ``zero_fraction``  float64 product of cover[child] / c with
+      c = cover[parent] if cover[parent] > 0 else 1.0, multiplied in
+      split order exactly as ``booster._tree_shap`` does.
+
+    Elements are ordered by the LAST split on their feature, the order
+    ``_tree_shap`` holds them in. Per path: ``path_ptr`` int32 [P+1]
+    offsets into the element arrays, ``value`` float64 leaf value x the
+    tree's scale, ``group`` int32 output group. ``bias`` float64
+    [n_groups] sums mean_val[0] * scale per group. ``max_len`` is the
+    longest path in elements; the ops refuse > SHAP_MAX_PATH_LEN.
+
+    scales / groups: one number for all trees, or one per tree.
+    """
+    import numpy as np
+
+    from xgboost_ray_amd.booster import _fill_node_means
+
+    T = len(trees)
+    scales = [float(scales)] * T if np.isscalar(scales) else list(scales)
+    groups = [0] * T if groups is None else [int(g) for g in groups]
+    n_groups = max(groups) + 1 if groups else 1
+    feature, lo, hi, miss_ok, zf = [], [], [], [], []
+    ptr, value, group, tree_id = [0], [], [], []
+    bias = np.zeros(n_groups, np.float64)
+    n_features = 0
+    for ti, t in enumerate(trees):
+        scale = scales[ti]
+        cover = t.cover.astype(np.float64)
+        mean_val = np.zeros(t.num_nodes, np.float64)
+        _fill_node_means(t, mean_val, cover)
+        bias[groups[ti]] += mean_val[0] * scale
+        stack = [(0, ())]
+        while stack:
+            nid, elems = stack.pop()
+            f = int(t.feat[nid])
+            if f < 0:
+                for e in elems:
+                    feature.append(e[0])
+                    lo.append(e[1])
+                    hi.append(e[2])
+                    miss_ok.append(e[3])
+                    zf.append(e[4])
+                ptr.append(len(feature))
+                # same arithmetic as _tree_shap's ``value * scale``
+                value.append(float(t.value[nid] * scale))
+                group.append(groups[ti])
+                tree_id.append(ti)
+                continue
+            n_features = max(n_features, f + 1)
+            left = int(t.left[nid])
+            c = cover[nid] if cover[nid] > 0 else 1.0
+            thr = np.float32(t.thr[nid])
+            dleft = bool(t.default_left[nid])
+            old = next((e for e in elems if e[0] == f), None)
+            rest = tuple(e for e in elems if e[0] != f)
+            if old is None:
+                old = (f, np.float32(-np.inf), np.float32(np.inf), True, 1.0)
+            # right child pushed first so leaves come out left to right
+            stack.append((left + 1, rest + ((
+                f, max(old[1], thr), old[2], old[3] and not dleft,
+                old[4] * cover[left + 1] / c),)))
+            stack.append((left, rest + ((
+                f, old[1], min(old[2], thr), old[3] and dleft,
+                old[4] * cover[left] / c),)))
+    path_ptr = np.asarray(ptr, np.int32)
+    lens = np.diff(path_ptr)
+    return {
+        "feature": np.asarray(feature, np.int32),
+        "lo": np.asarray(lo, np.float32),
+        "hi": np.asarray(hi, np.float32),
+        "miss_ok": np.asarray(miss_ok, np.uint8),
+        "zero_fraction": np.asarray(zf, np.float64),
+        "path_ptr": path_ptr,
+        "value": np.asarray(value, np.float64),
+        "group": np.asarray(group, np.int32),
+        "tree": np.asarray(tree_id, np.int32),
+        "bias": bias,
+        "n_groups": n_groups,
+        "n_features": n_features,
+        "max_len": int(lens.max()) if len(lens) else 0,
+    }
+
+
+def _shap_check(X, paths, n_groups):
+    if paths["max_len"] > SHAP_MAX_PATH_LEN:
+        raise ValueError(
+            f"tree_shap: a path has {paths['max_len']} unique features, "
+            f"the path-form op supports {SHAP_MAX_PATH_LEN}"
+        )
+    if paths["n_features"] > X.shape[1]:
+        raise ValueError(
+            f"tree_shap: forest splits on feature {paths['n_features'] - 1}"
+            f" but X has {X.shape[1]} columns"
+        )
+    if paths["n_groups"] > n_groups:
+        raise ValueError("tree_shap: path group outside n_groups")
+
+
+def _shap_one_fractions(Xn, paths, e0, e1):
+    """[m, n] float64: 1 where the row follows the element's splits."""
+    import numpy as np
+
+    x = Xn[:, paths["feature"][e0:e1]].T  # [m, n] float32
+    lo = paths["lo"][e0:e1, None]
+    hi = paths["hi"][e0:e1, None]
+    inside = (x >= lo) & ((x < hi) | np.isposinf(hi))
+    miss = paths["miss_ok"][e0:e1, None].astype(bool)
+    return np.where(np.isnan(x), miss, inside).astype(np.float64)
+
+
+def _shap_extend(z, o):
+    """Permutation weights of a whole path: ``_tree_shap``'s EXTEND run
+    over the dummy root element and then every element. [m+1, n]."""
+    import numpy as np
+
+    m, n = o.shape
+    w = np.zeros((m + 1, n), np.float64)
+    w[0] = 1.0
+    for k in range(1, m + 1):
+        pz, po = z[k - 1], o[k - 1]
+        ln = k + 1
+        for i in range(k - 1, -1, -1):
+            w[i + 1] += po * w[i] * (i + 1) / ln
+            w[i] = pz * w[i] * (ln - 1 - i) / ln
+    return w
+
+
+def _shap_unwound_sum(w, ln, pz, po):
+    """``_tree_shap``'s unwind_sum for an element (pz scalar, po [n] of
+    0/1) of a path with weights w[0..ln]; both branches, selected by po."""
+    import numpy as np
+
+    hot = np.zeros(w.shape[1], np.float64)
+    nxt = w[ln]
+    for j in range(ln - 1, -1, -1):
+        tmp = nxt * (ln + 1) / ((j + 1) * 1.0)
+        hot = hot + tmp
+        nxt = w[j] - tmp * pz * (ln - j) / (ln + 1)
+    cold = np.zeros(w.shape[1], np.float64)
+    for j in range(ln):
+        cold = cold + w[j] * (ln + 1) / (pz * (ln - j))
+    return np.where(po != 0.0, hot, cold)
+
+
+def _shap_unwind(w, ln, pz, po):
+    """Weights of the path with one element removed ([ln, n])."""
+    import numpy as np
+
+    hot = np.empty((ln, w.shape[1]), np.float64)
+    cold = np.empty_like(hot)
+    nxt = w[ln]
+    for j in range(ln - 1, -1, -1):
+        tmp = nxt * (ln + 1) / ((j + 1) * 1.0)
+        nxt = w[j] - tmp * pz * (ln - j) / (ln + 1)
+        hot[j] = tmp
+        cold[j] = w[j] * (ln + 1) / (pz * (ln - j))
+    return np.where(po[None, :] != 0.0, hot, cold)
+
+
+def tree_shap(X, paths, n_groups, out, max_out_bytes=None):
+    """Path-form exact TreeSHAP, float64 numpy, vectorised over rows:
+    the numerics oracle of the HIP kernel (contract: ``ops.tree_shap``).
+
+    A path on which some element has one_fraction == 0 AND
+    zero_fraction == 0 contributes nothing for that row (every subset
+    term carries one of the two factors) and is skipped - the recursion
+    divides 0 by 0 there. ``max_out_bytes`` is the GPU wrapper's chunk
+    bound and means nothing here."""
+    import numpy as np
+
+    Xn, outn = _as_numpy(X), _as_numpy(out)
+    _shap_check(Xn, paths, n_groups)
+    ptr, zf = paths["path_ptr"], paths["zero_fraction"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for p in range(len(ptr) - 1):
+            e0, e1 = int(ptr[p]), int(ptr[p + 1])
+            m = e1 - e0
+            if m == 0:
+                continue
+            z = zf[e0:e1]
+            o = _shap_one_fractions(Xn, paths, e0, e1)
+            dead = ((o == 0.0) & (z[:, None] == 0.0)).any(axis=0)
+            w = _shap_extend(z, o)
+            v = paths["value"][p]
+            dest = outn[:, int(paths["group"][p]), :]
+            for i in range(m):
+                s = _shap_unwound_sum(w, m, z[i], o[i])
+                dest[:, int(paths["feature"][e0 + i])] += np.where(
+                    dead, 0.0, s * (o[i] - z[i]) * v)
+    return out
+
+
+def tree_shap_interactions(X, paths, out, max_out_bytes=None):
+    """Raw off-diagonal SHAP interaction terms in path form (contract:
+    ``ops.tree_shap_interactions``). For a path with elements E and leaf
+    value v, every c in E and j in E \\ {c} adds
+    (one_c - zero_c) / 2 * unwound_sum(E \\ {c}, j) * (one_j - zero_j) * v
+    to out[:, feature_c, feature_j] - what ``_tree_shap`` yields as
+    (condition=+1 pass - condition=-1 pass) / 2."""
+    import numpy as np
+
+    Xn, outn = _as_numpy(X), _as_numpy(out)
+    _shap_check(Xn, paths, 1)
+    ptr, zf = paths["path_ptr"], paths["zero_fraction"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for p in range(len(ptr) - 1):
+            e0, e1 = int(ptr[p]), int(ptr[p + 1])
+            m = e1 - e0
+            if m < 2:
+                continue
+            z = zf[e0:e1]
+            o = _shap_one_fractions(Xn, paths, e0, e1)
+            dead = ((o == 0.0) & (z[:, None] == 0.0)).any(axis=0)
+            w = _shap_extend(z, o)
+            v = paths["value"][p]
+            feat = paths["feature"][e0:e1]
+            for c in range(m):
+                w2 = _shap_unwind(w, m, z[c], o[c])
+                half = (o[c] - z[c]) / 2.0
+                for j in range(m):
+                    if j == c:
+                        continue
+                    s = _shap_unwound_sum(w2, m - 1, z[j], o[j])
+                    outn[:, int(feat[c]), int(feat[j])] += np.where(
+                        dead, 0.0, half * s * (o[j] - z[j]) * v)
+    return out

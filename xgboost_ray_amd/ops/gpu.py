@@ -298,3 +298,81 @@ def eval_auc_hist(margin, label, n_bins):
     return _load().eval_auc_hist(
         margin.contiguous(), label.contiguous().float(), int(n_bins)
     )
+
+
+# -- path-form TreeSHAP ------------------------------------------------------
+# Rows per launch are bounded: the float64 device output of one launch
+# stays under these sizes (interactions write (F+1)^2 values per row) and
+# each chunk is added into ``out`` before the next one runs.
+SHAP_OUT_BYTES = 1 << 30
+SHAP_INTER_OUT_BYTES = 1 << 28
+
+
+def shap_tile_elems():
+    """Path elements one LDS tile of the kernel holds."""
+    return int(_load().SHAP_TILE_ELEMS)
+
+
+def _shap_device_paths(paths, dev):
+    """Upload (once per device) the path arrays in the kernel's packing."""
+    import numpy as np
+
+    key = str(dev)
+    cache = paths.setdefault("_device", {})
+    if key not in cache:
+        E = len(paths["feature"])
+        elem = np.zeros((E, 4), np.int32)
+        elem[:, 0] = paths["feature"] | (
+            paths["miss_ok"].astype(np.int32) << 31)
+        elem[:, 1] = paths["lo"].view(np.int32)
+        elem[:, 2] = paths["hi"].view(np.int32)
+        cache[key] = (
+            torch.from_numpy(elem).to(dev),
+            torch.from_numpy(paths["zero_fraction"]).to(dev),
+            torch.from_numpy(np.ascontiguousarray(paths["path_ptr"])),
+            torch.from_numpy(paths["value"]).to(dev),
+            torch.from_numpy(paths["group"]).to(dev),
+        )
+    return cache[key]
+
+
+def _tree_shap_chunked(X, paths, n_groups, out, interactions, max_out_bytes):
+    from xgboost_ray_amd.ops import cpu
+
+    cpu._shap_check(X, paths, n_groups)
+    dev = X.device
+    X = X.contiguous()
+    n = X.shape[0]
+    elem, zf, ptr, val, grp = _shap_device_paths(paths, dev)
+    per_row = out[0].numel() if n else 1
+    chunk = max(1, int(max_out_bytes) // (8 * per_row))
+    for s in range(0, n, chunk):
+        e = min(n, s + chunk)
+        direct = out.is_cuda and out.is_contiguous()
+        buf = out[s:e] if direct else torch.zeros(
+            (e - s,) + tuple(out.shape[1:]), dtype=torch.float64, device=dev)
+        _load().tree_shap(X[s:e], elem, zf, ptr, val, grp, buf,
+                          int(n_groups), bool(interactions))
+        if not direct:
+            # copy this chunk out before the next one runs
+            out[s:e] += buf.to(out.device)
+    return out
+
+
+def tree_shap(X, paths, n_groups, out, max_out_bytes=None):
+    expect = (X.shape[0], int(n_groups), X.shape[1] + 1)
+    if tuple(out.shape) != expect or out.dtype != torch.float64:
+        raise ValueError(f"tree_shap: out must be float64 {expect}")
+    return _tree_shap_chunked(
+        X, paths, n_groups, out, False,
+        SHAP_OUT_BYTES if max_out_bytes is None else max_out_bytes)
+
+
+def tree_shap_interactions(X, paths, out, max_out_bytes=None):
+    expect = (X.shape[0], X.shape[1] + 1, X.shape[1] + 1)
+    if tuple(out.shape) != expect or out.dtype != torch.float64:
+        raise ValueError(f"tree_shap_interactions: out must be float64 "
+                         f"{expect}")
+    return _tree_shap_chunked(
+        X, paths, 1, out, True,
+        SHAP_INTER_OUT_BYTES if max_out_bytes is None else max_out_bytes)

@@ -11,6 +11,8 @@
 //     to the CPU torch reference (same add/divide order)
 //   - partition_rows: stable two-pass partition (ballot prefix + scatter;
 //     two-phase begin/finish entry, device-planned variant)
+//   - apply_tree_binned: row-order walk of one finished tree over the
+//     binned matrix, leaf value added into the margin (the tree finish)
 //   - grad_fused:     fused objective gradient + |g|/|h| block maxes
 //   - predict_trees:  packed-node tree walk (LDS tree-tiled serving path)
 //   - tree_shap:      exact TreeSHAP contributions / interactions in path
@@ -49,18 +51,84 @@ static inline bool on_gpu(const torch::Tensor& t) { return t.is_cuda(); }
 // int32 pairs: |q| <= 2^30 by scale construction, so int32 holds each
 // row exactly and int64 accumulators hold any sum - half the gradient
 // traffic of int64 pairs at identical numerics.
-__global__ void quantize_gpair_kernel(const float2* __restrict__ gpair,
-                                      int2* __restrict__ out,
-                                      double scale_g, double scale_h,
-                                      int64_t n) {
+// SUMS: the pass also emits the column sums of what it wrote (the root
+// node's quantized gradient totals), so nobody re-reads `out` for them.
+// Each block writes its own int64 pair to partials[2 * blockIdx.x ..]; a
+// single small block adds the partials up (no same-address global atomics).
+// Integer sums are order-free: the result equals out.sum(0) exactly.
+#define QUANT_THREADS 256
+template <bool SUMS>
+__global__ __launch_bounds__(QUANT_THREADS) void quantize_gpair_kernel(
+    const float2* __restrict__ gpair, int2* __restrict__ out, double scale_g,
+    double scale_h, int64_t n, long long* __restrict__ partials) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  long long sg = 0, sh = 0;
   for (; i < n; i += stride) {
     float2 gp = gpair[i];
     int2 q;
     q.x = (int)llrint((double)gp.x * scale_g);
     q.y = (int)llrint((double)gp.y * scale_h);
     out[i] = q;
+    if (SUMS) {
+      sg += q.x;
+      sh += q.y;
+    }
+  }
+  if (SUMS) {
+    #pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+      sg += __shfl_down(sg, off, WAVE);
+      sh += __shfl_down(sh, off, WAVE);
+    }
+    __shared__ long long wsum[QUANT_THREADS / WAVE][2];
+    const int wave_id = threadIdx.x / WAVE;
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+      wsum[wave_id][0] = sg;
+      wsum[wave_id][1] = sh;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      long long tg = 0, th = 0;
+      for (int w = 0; w < QUANT_THREADS / WAVE; ++w) {
+        tg += wsum[w][0];
+        th += wsum[w][1];
+      }
+      partials[2 * blockIdx.x] = tg;
+      partials[2 * blockIdx.x + 1] = th;
+    }
+  }
+}
+
+// one block: sums[0..1] = column sums of partials [n_blocks, 2]
+__global__ __launch_bounds__(QUANT_THREADS) void reduce_pair_partials_kernel(
+    const long long* __restrict__ partials, int n_blocks,
+    long long* __restrict__ sums) {
+  long long sg = 0, sh = 0;
+  for (int i = threadIdx.x; i < n_blocks; i += QUANT_THREADS) {
+    sg += partials[2 * i];
+    sh += partials[2 * i + 1];
+  }
+  #pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    sg += __shfl_down(sg, off, WAVE);
+    sh += __shfl_down(sh, off, WAVE);
+  }
+  __shared__ long long wsum[QUANT_THREADS / WAVE][2];
+  const int wave_id = threadIdx.x / WAVE;
+  if ((threadIdx.x & (WAVE - 1)) == 0) {
+    wsum[wave_id][0] = sg;
+    wsum[wave_id][1] = sh;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    long long tg = 0, th = 0;
+    for (int w = 0; w < QUANT_THREADS / WAVE; ++w) {
+      tg += wsum[w][0];
+      th += wsum[w][1];
+    }
+    sums[0] = tg;
+    sums[1] = th;
   }
 }
 
@@ -1170,6 +1238,126 @@ __global__ void update_margins_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// apply_tree_binned: margin[r * margin_stride] += value[leaf(r)] in ROW
+// order, the leaf found by walking the finished tree over the row's own
+// bin bytes (the predicate is partition_count_kernel's, so every row lands
+// in the leaf the partition put it in). One coalesced pass over bins and
+// margin replaces the last-level partition plus the scattered
+// update_margins read-modify-write.
+//   packed node (8 B): x = feature | split_bin << 16 | default_left << 24
+//                          | is_leaf << 31
+//                      y = left child index, or the leaf's f32 value bits
+// The node table is staged into LDS when it fits ATB_LDS_NODES (depth 12 =
+// 8191 nodes = 64 KB); larger trees read the same table from global memory.
+// NDW > 0: the row is NDW dwords, loaded whole (coalesced 16 B loads) into
+// registers held as ONE clang vector value; a level's bin byte is a
+// variable-index element of that vector, which the backend turns into a
+// compare/select chain over the registers (a runtime-indexed ARRAY, or a
+// hand-written select chain over one, goes to scratch: the optimizer folds
+// the selects back into an indexed load). NDW == 0: any row stride,
+// one byte load per level from the row's already-touched lines.
+// The walk is bounded by max_steps (<= n_nodes): a malformed table cannot
+// spin, and a row that has not reached a leaf by then is left untouched.
+// ---------------------------------------------------------------------------
+#define ATB_THREADS 256
+#define ATB_LDS_NODES 8192
+#define ATB_LEAF 0x80000000u
+
+// row registers: one clang vector of NV dwords (12-dword rows ride in 16)
+template <int NV>
+struct AtbRow {
+  typedef uint32_t type __attribute__((ext_vector_type(NV)));
+};
+
+template <int NDW, int R, bool LDS_TAB>
+__global__ __launch_bounds__(ATB_THREADS) void apply_tree_binned_kernel(
+    const uint8_t* __restrict__ bins, const uint2* __restrict__ nodes,
+    float* __restrict__ margin, int64_t n, int64_t row_stride,
+    int64_t margin_stride, int n_nodes, int max_steps) {
+  extern __shared__ __align__(16) uint2 atb_lds[];
+  const uint2* tab = nodes;
+  if (LDS_TAB) {
+    for (int i = threadIdx.x; i < n_nodes; i += ATB_THREADS)
+      atb_lds[i] = nodes[i];
+    __syncthreads();
+    tab = atb_lds;
+  }
+  const int64_t chunk = (int64_t)ATB_THREADS * R;
+  const int64_t n_chunks = (n + chunk - 1) / chunk;
+  for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const int64_t r0 = c * chunk + threadIdx.x;
+    bool valid[R];
+    uint2 nd[R];
+    constexpr int NV = NDW == 0 ? 1 : (NDW == 12 ? 16 : NDW);
+    typename AtbRow<NV>::type w[R];
+    #pragma unroll
+    for (int s = 0; s < R; ++s) {
+      const int64_t r = r0 + (int64_t)s * ATB_THREADS;
+      valid[s] = r < n;
+      if (NDW > 0) {
+        const uint4* rp = reinterpret_cast<const uint4*>(
+            bins + (valid[s] ? r : 0) * row_stride);
+        typename AtbRow<NV>::type row = 0;
+        #pragma unroll
+        for (int q = 0; q < NDW / 4; ++q) {
+          const uint4 v = rp[q];
+          row[4 * q + 0] = v.x;
+          row[4 * q + 1] = v.y;
+          row[4 * q + 2] = v.z;
+          row[4 * q + 3] = v.w;
+        }
+        w[s] = row;
+      }
+    }
+    const uint2 root = tab[0];
+    #pragma unroll
+    for (int s = 0; s < R; ++s) {
+      nd[s] = root;
+      if (!valid[s]) nd[s].x = ATB_LEAF;  // parked: never walks or writes
+    }
+    for (int step = 0; step < max_steps; ++step) {
+      bool any = false;
+      uint32_t b[R];
+      // issue every row's byte fetch before any is consumed
+      #pragma unroll
+      for (int s = 0; s < R; ++s) {
+        const uint32_t feat = nd[s].x & 0xFFFFu;
+        if (NDW > 0) {
+          // variable-index vector element: the backend expands it into
+          // a compare/select chain over the row's registers
+          b[s] = (w[s][(feat >> 2) & (NV - 1)] >> ((feat & 3u) * 8u)) & 0xFFu;
+        } else {
+          b[s] = 255u;
+          if (!(nd[s].x & ATB_LEAF)) {
+            const int64_t r = r0 + (int64_t)s * ATB_THREADS;
+            b[s] = bins[r * row_stride + feat];
+          }
+        }
+      }
+      #pragma unroll
+      for (int s = 0; s < R; ++s) {
+        if (nd[s].x & ATB_LEAF) continue;
+        const uint32_t sbin = (nd[s].x >> 16) & 0xFFu;
+        const bool dl = ((nd[s].x >> 24) & 1u) != 0;
+        const bool go_left = (b[s] == 255u) ? dl : (b[s] <= sbin);
+        uint32_t child = nd[s].y + (go_left ? 0u : 1u);
+        // host-validated; the clamp only keeps a bad table in bounds
+        child = child < (uint32_t)n_nodes ? child : 0u;
+        nd[s] = tab[child];
+        any = true;
+      }
+      if (!any) break;
+    }
+    #pragma unroll
+    for (int s = 0; s < R; ++s) {
+      const int64_t r = r0 + (int64_t)s * ATB_THREADS;
+      if (valid[s] && (nd[s].x & ATB_LEAF))
+        margin[r * margin_stride] += __uint_as_float(nd[s].y);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // leaf_quantile_hist: one pass of the MSB-first radix select behind the
 // adaptive (exact weighted quantile) leaves of reg:quantileerror.
 //   hist[leaf][digit] += W[row]  over the leaf's rows whose order-preserving
@@ -1348,11 +1536,43 @@ torch::Tensor quantize_gpair(torch::Tensor gpair, double scale_g, double scale_h
   int64_t n = gpair.size(0);
   if (n == 0) return out;
   auto stream = c10::hip::getCurrentHIPStream();
-  int64_t blocks = std::min<int64_t>(ceil_div(n, 256), 8192);
-  hipLaunchKernelGGL(quantize_gpair_kernel, dim3(blocks), dim3(256), 0,
-                     stream.stream(), (const float2*)gpair.data_ptr<float>(),
-                     (int2*)out.data_ptr<int32_t>(), scale_g, scale_h, n);
+  int64_t blocks = std::min<int64_t>(ceil_div(n, QUANT_THREADS), 8192);
+  hipLaunchKernelGGL(quantize_gpair_kernel<false>, dim3(blocks),
+                     dim3(QUANT_THREADS), 0, stream.stream(),
+                     (const float2*)gpair.data_ptr<float>(),
+                     (int2*)out.data_ptr<int32_t>(), scale_g, scale_h, n,
+                     (long long*)nullptr);
   return out;
+}
+
+// quantize_gpair that also returns int64 [2] = out.sum(0) (device).
+std::vector<torch::Tensor> quantize_gpair_sums(torch::Tensor gpair,
+                                               double scale_g,
+                                               double scale_h) {
+  TORCH_CHECK(on_gpu(gpair) && gpair.dtype() == torch::kFloat32);
+  TORCH_CHECK(gpair.is_contiguous() && gpair.dim() == 2 && gpair.size(1) == 2,
+              "quantize_gpair_sums: gpair must be contiguous [n, 2]");
+  auto out = torch::empty_like(gpair, gpair.options().dtype(torch::kInt32));
+  auto optsl = gpair.options().dtype(torch::kInt64);
+  int64_t n = gpair.size(0);
+  if (n == 0) return {out, torch::zeros({2}, optsl)};
+  auto sums = torch::empty({2}, optsl);
+  auto stream = c10::hip::getCurrentHIPStream();
+  int64_t blocks = std::min<int64_t>(ceil_div(n, QUANT_THREADS), 8192);
+  auto partials = torch::empty({blocks, 2}, optsl);
+  hipLaunchKernelGGL(quantize_gpair_kernel<true>, dim3(blocks),
+                     dim3(QUANT_THREADS), 0, stream.stream(),
+                     (const float2*)gpair.data_ptr<float>(),
+                     (int2*)out.data_ptr<int32_t>(), scale_g, scale_h, n,
+                     reinterpret_cast<long long*>(
+                         partials.data_ptr<int64_t>()));
+  hipLaunchKernelGGL(reduce_pair_partials_kernel, dim3(1),
+                     dim3(QUANT_THREADS), 0, stream.stream(),
+                     reinterpret_cast<const long long*>(
+                         partials.data_ptr<int64_t>()),
+                     (int)blocks,
+                     reinterpret_cast<long long*>(sums.data_ptr<int64_t>()));
+  return {out, sums};
 }
 
 torch::Tensor bin_matrix(torch::Tensor values, torch::Tensor cuts_flat,
@@ -2471,6 +2691,125 @@ void update_margins(torch::Tensor margin, torch::Tensor ridx,
                      lv.data_ptr<float>(), K);
 }
 
+template <int NDW, int R>
+static void launch_apply_tree_binned(bool lds, int grid, size_t lds_bytes,
+                                     hipStream_t s, const uint8_t* bins,
+                                     const uint2* nodes, float* margin,
+                                     int64_t n, int64_t row_stride,
+                                     int64_t margin_stride, int n_nodes) {
+  if (lds) {
+    hipLaunchKernelGGL((apply_tree_binned_kernel<NDW, R, true>), dim3(grid),
+                       dim3(ATB_THREADS), lds_bytes, s, bins, nodes, margin,
+                       n, row_stride, margin_stride, n_nodes, n_nodes);
+  } else {
+    hipLaunchKernelGGL((apply_tree_binned_kernel<NDW, R, false>), dim3(grid),
+                       dim3(ATB_THREADS), 0, s, bins, nodes, margin, n,
+                       row_stride, margin_stride, n_nodes, n_nodes);
+  }
+}
+
+// margin[r * margin_stride] += value[leaf of row r] for every row of the
+// binned matrix. The tree arrives as HOST arrays (feat < 0 marks a leaf)
+// and is packed into ONE pinned H2D; `margin` may be a strided column view.
+void apply_tree_binned(torch::Tensor bins, torch::Tensor margin,
+                       torch::Tensor feat, torch::Tensor split_bin,
+                       torch::Tensor left, torch::Tensor default_left,
+                       torch::Tensor value) {
+  TORCH_CHECK(on_gpu(bins) && bins.dtype() == torch::kUInt8 &&
+                  bins.dim() == 2 && bins.stride(1) == 1,
+              "apply_tree_binned: bins must be a GPU uint8 [n, F] matrix");
+  TORCH_CHECK(on_gpu(margin) && margin.dtype() == torch::kFloat32 &&
+                  margin.dim() == 1,
+              "apply_tree_binned: margin must be a GPU f32 vector (view)");
+  const int64_t n = bins.size(0);
+  const int64_t F = bins.size(1);
+  TORCH_CHECK(margin.size(0) == n, "apply_tree_binned: margin has ",
+              margin.size(0), " rows, bins ", n);
+  const int64_t row_stride = n > 1 ? bins.stride(0) : F;
+  const int64_t margin_stride = n > 1 ? margin.stride(0) : 1;
+  TORCH_CHECK(row_stride >= F && margin_stride >= 1);
+  const int64_t n_nodes = feat.size(0);
+  TORCH_CHECK(n_nodes >= 1 && n_nodes < (int64_t)1 << 30);
+  auto feat_c = feat.to(torch::kCPU).to(torch::kInt32).contiguous();
+  auto sbin_c = split_bin.to(torch::kCPU).to(torch::kInt32).contiguous();
+  auto left_c = left.to(torch::kCPU).to(torch::kInt32).contiguous();
+  auto dl_c = default_left.to(torch::kCPU).to(torch::kUInt8).contiguous();
+  auto val_c = value.to(torch::kCPU).to(torch::kFloat32).contiguous();
+  TORCH_CHECK(sbin_c.size(0) == n_nodes && left_c.size(0) == n_nodes &&
+                  dl_c.size(0) == n_nodes && val_c.size(0) == n_nodes,
+              "apply_tree_binned: tree arrays differ in length");
+  if (n == 0) return;
+  static thread_local PinnedStager atb_node_stager;
+  auto nodes_cpu = atb_node_stager.get(n_nodes);
+  {
+    const int32_t* fp = feat_c.data_ptr<int32_t>();
+    const int32_t* bp = sbin_c.data_ptr<int32_t>();
+    const int32_t* lp = left_c.data_ptr<int32_t>();
+    const uint8_t* dp = dl_c.data_ptr<uint8_t>();
+    const float* vp = val_c.data_ptr<float>();
+    uint32_t* np = reinterpret_cast<uint32_t*>(nodes_cpu.data_ptr<int64_t>());
+    for (int64_t i = 0; i < n_nodes; ++i) {
+      if (fp[i] < 0) {
+        np[2 * i] = ATB_LEAF;
+        std::memcpy(&np[2 * i + 1], &vp[i], 4);
+      } else {
+        TORCH_CHECK(fp[i] < F && fp[i] < 65536 && bp[i] >= 0 &&
+                        bp[i] <= 255 && lp[i] > 0 && lp[i] + 1 < n_nodes,
+                    "apply_tree_binned: malformed node ", i);
+        np[2 * i] = (uint32_t)fp[i] | ((uint32_t)bp[i] << 16) |
+                    (dp[i] ? (1u << 24) : 0u);
+        np[2 * i + 1] = (uint32_t)lp[i];
+      }
+    }
+  }
+  auto nodes = nodes_cpu.to(bins.device(), /*non_blocking=*/true);
+  auto stream = c10::hip::getCurrentHIPStream();
+  atb_node_stager.mark(stream.stream());
+  const uint8_t* bptr = bins.data_ptr<uint8_t>();
+  const uint2* nptr = reinterpret_cast<const uint2*>(nodes.data_ptr<int64_t>());
+  float* mptr = margin.data_ptr<float>();
+  const bool lds = n_nodes <= ATB_LDS_NODES;
+  const size_t lds_bytes = lds ? (size_t)n_nodes * sizeof(uint2) : 0;
+  // whole-row register form: 16 B aligned rows of 4, 8, 12 or 16 dwords
+  // whose padding lies inside the allocation
+  const int64_t avail =
+      (int64_t)bins.storage().nbytes() - bins.storage_offset();
+  const bool vec = (reinterpret_cast<uintptr_t>(bptr) % 16 == 0) &&
+                   (row_stride % 16 == 0) && row_stride <= 64 &&
+                   n * row_stride <= avail;
+  const int ndw = vec ? (int)(row_stride / 4) : 0;
+  const int R = (ndw == 12 || ndw == 16) ? 4 : 8;
+  // one chunk per workgroup while the table is small (<= 16 KB to stage);
+  // a big table is staged by a chip-filling grid that strides over chunks
+  const int64_t chunks = ceil_div(n, (int64_t)ATB_THREADS * R);
+  const int grid = (int)std::min<int64_t>(
+      chunks, n_nodes <= 2048 ? (int64_t)1 << 30 : 1024);
+  hipStream_t s = stream.stream();
+  const int nn = (int)n_nodes;
+  switch (ndw) {
+    case 4:
+      launch_apply_tree_binned<4, 8>(lds, grid, lds_bytes, s, bptr, nptr,
+                                     mptr, n, row_stride, margin_stride, nn);
+      break;
+    case 8:
+      launch_apply_tree_binned<8, 8>(lds, grid, lds_bytes, s, bptr, nptr,
+                                     mptr, n, row_stride, margin_stride, nn);
+      break;
+    case 12:
+      launch_apply_tree_binned<12, 4>(lds, grid, lds_bytes, s, bptr, nptr,
+                                      mptr, n, row_stride, margin_stride, nn);
+      break;
+    case 16:
+      launch_apply_tree_binned<16, 4>(lds, grid, lds_bytes, s, bptr, nptr,
+                                      mptr, n, row_stride, margin_stride, nn);
+      break;
+    default:
+      launch_apply_tree_binned<0, 8>(lds, grid, lds_bytes, s, bptr, nptr,
+                                     mptr, n, row_stride, margin_stride, nn);
+  }
+  CHECK_HIP(hipGetLastError());
+}
+
 static_assert(LQH_THREADS == 256, "flush maps one thread to one bin");
 
 // One radix-select pass over the leaf segments; accumulates into hist
@@ -2882,6 +3221,10 @@ std::vector<torch::Tensor> depth_step(
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("quantize_gpair", &quantize_gpair, "quantize gradient pairs");
+  m.def("quantize_gpair_sums", &quantize_gpair_sums,
+        "quantize gradient pairs, also returning their int64 column sums");
+  m.def("apply_tree_binned", &apply_tree_binned,
+        "row-order tree walk over the binned matrix, added into the margin");
   m.def("grad_fused", &grad_fused, "fused objective gradient + absmax");
   m.def("eval_logloss", &eval_logloss, "fused logloss eval");
   m.def("eval_auc_hist", &eval_auc_hist, "fused AUC score histograms");

@@ -31,6 +31,13 @@ from xgboost_ray_amd.engine.quantile import BinnedMatrix
 
 _QUANT_BITS = 30
 
+# The row-order tree finish (RXGB_ROW_FINISH) is selected up to this row
+# stride of the binned matrix, in bytes: there apply_tree_binned holds the
+# whole row in registers and streams the matrix once. Wider rows take one
+# byte load per level from scattered sectors of a long row and keep the
+# legacy finish (numbers: profiles/README.md, round-3 pass 1).
+_ROW_FINISH_MAX_STRIDE = 64
+
 
 @dataclass
 class TrainParams:
@@ -144,10 +151,13 @@ class _TreeArrays:
     lists of per-node appends; fields are written by vectorized numpy
     fancy-indexing per depth)."""
 
-    __slots__ = ("feat", "thr", "left", "dl", "val", "gain", "cover",
-                 "parent", "n", "cap")
+    __slots__ = ("feat", "thr", "split_bin", "left", "dl", "val", "gain",
+                 "cover", "parent", "n", "cap")
     _FIELDS = (
         ("feat", -1, np.int64), ("thr", 0.0, np.float64),
+        # bin index behind thr ("bin <= split_bin" goes left): the binned
+        # row-order walk needs it; it is not part of the Tree
+        ("split_bin", 0, np.int64),
         ("left", -1, np.int64), ("dl", 0, np.int64),
         ("val", 0.0, np.float64), ("gain", 0.0, np.float64),
         ("cover", 0.0, np.float64), ("parent", -1, np.int64),
@@ -489,6 +499,15 @@ class BoostingEngine:
     def _add_tree_margin_binned(self, t: Tree, split_bin, margin_view):
         bins = self.dtrain.bins
         n = bins.shape[0]
+        if bins.is_cuda:
+            # one HIP row-order walk (same predicate, same f32 add) in
+            # place of the per-level torch loop below, which stays as the
+            # CPU path
+            ops.apply_tree_binned(
+                bins, margin_view, t.feat, split_bin, t.left,
+                t.default_left, t.value,
+            )
+            return
         cur = torch.zeros(n, dtype=torch.int64, device=self.device)
         feat = torch.from_numpy(t.feat.astype(np.int64)).to(self.device)
         sbin = torch.as_tensor(split_bin, dtype=torch.int64, device=self.device)
@@ -750,6 +769,14 @@ class BoostingEngine:
             mx = mx_d.cpu()
         scale_g = float(2.0**_QUANT_BITS) / max(float(mx[0]), 1e-300)
         scale_h = float(2.0**_QUANT_BITS) / max(float(mx[1]), 1e-300)
+        self._gq_sum = None
+        if gpair.is_cuda:
+            # the quantize pass emits the column sums of what it writes:
+            # the root totals of an unsampled tree, without re-reading gq
+            gq, self._gq_sum = ops.quantize_gpair_sums(
+                gpair, scale_g, scale_h
+            )
+            return gq, scale_g, scale_h
         return ops.quantize_gpair(gpair, scale_g, scale_h), scale_g, scale_h
 
     def _sample_rows(self, it: int, cls: int) -> torch.Tensor:
@@ -894,8 +921,11 @@ class BoostingEngine:
         if n_local == 0:
             root_sum = torch.zeros(2, dtype=torch.int64, device=self.device)
         elif n_local == self.dtrain.n_rows:
-            # no row sampling: ridx is the identity - skip the per-row gather
-            root_sum = gq.sum(dim=0, dtype=torch.int64)
+            # no row sampling: ridx is the identity - skip the per-row
+            # gather; on GPU the quantize pass already summed gq
+            root_sum = getattr(self, "_gq_sum", None)
+            if root_sum is None:
+                root_sum = gq.sum(dim=0, dtype=torch.int64)
         else:
             root_sum = gq[ridx.long()].sum(dim=0, dtype=torch.int64)
         if self.coll.is_distributed:
@@ -935,6 +965,23 @@ class BoostingEngine:
         use_fused_loop = (
             self.device.type == "cuda"
             and _os2.environ.get("RXGB_ONE_SYNC", "1") != "0"
+        )
+        # row-order finish (GPU, per tree like RXGB_ONE_SYNC): the margin
+        # update is one apply_tree_binned walk over the binned matrix in
+        # row order, so the last level launches no partition at all - its
+        # children are leaves, and nothing but the scattered per-segment
+        # margin update ever read the permuted ridx/gseg or the child row
+        # counts. Adaptive objectives (reg:quantileerror) need the
+        # per-leaf row lists and keep the legacy finish.
+        # RXGB_ROW_FINISH=0 restores the legacy finish exactly; =2 lifts
+        # the row-stride rule (measurement only).
+        _rf = _os2.environ.get("RXGB_ROW_FINISH", "1")
+        row_finish = (
+            self.device.type == "cuda"
+            and not self._adaptive
+            and _rf != "0"
+            and (_rf == "2"
+                 or self.dtrain.bins.stride(0) <= _ROW_FINISH_MAX_STRIDE)
         )
         ridx_bufs = None
         cur_buf = 0
@@ -1023,6 +1070,12 @@ class BoostingEngine:
             use_depth_step = (
                 use_fused_loop and not self.coll.is_distributed
                 and _os2.environ.get("RXGB_DEPTH_STEP") == "1"
+            )
+            # row-order finish: this level's children are leaves, so only
+            # the histogram, the scan and the split pull run for it
+            last_level = (
+                row_finish and not use_depth_step
+                and depth == self.p.max_depth - 1
             )
             if use_depth_step:
                 # one C++ call per depth: stage + zero + hist + derive +
@@ -1189,7 +1242,7 @@ class BoostingEngine:
                 # synced past the scatter and was SLOWER - see
                 # profiles/README.md pass 5/8). RXGB_ONE_SYNC=0 restores
                 # the 2-sync path.
-                use_fused = use_fused_loop
+                use_fused = use_fused_loop and not last_level
                 lc_full = None
                 if use_fused:
                     packed_dev = ops.find_splits(
@@ -1279,7 +1332,8 @@ class BoostingEngine:
             sb32 = bbin[okf].astype(np.int32)
             sdl8 = bdl[okf].astype(np.uint8)
             part_ctx = None
-            if lc_full is None and self.device.type == "cuda":
+            if (lc_full is None and self.device.type == "cuda"
+                    and not last_level):
                 part_ctx = ops.partition_begin(
                     self.dtrain.bins,
                     ridx,
@@ -1316,6 +1370,7 @@ class BoostingEngine:
             )
             ta.feat[nids_ok] = f_ok
             ta.thr[nids_ok] = thr_ok
+            ta.split_bin[nids_ok] = b_ok
             ta.left[nids_ok] = lids
             ta.dl[nids_ok] = bdl[okf]
             ta.gain[nids_ok] = gain[okf].astype(np.float64)
@@ -1330,6 +1385,10 @@ class BoostingEngine:
                 # per-split-node left counts rode the single pull, in
                 # the same ascending-okf order the plan kernel compacted
                 lc = lc_full[:n_split].astype(np.int64)
+            elif last_level:
+                # no partition ran: the leaf children's segment starts and
+                # counts below are placeholders nothing reads
+                lc = np.zeros(n_split, np.int64)
             elif part_ctx is not None:
                 ridx, left_counts, gseg = ops.partition_finish(part_ctx)
                 lc = left_counts.numpy().astype(np.int64)
@@ -1458,7 +1517,19 @@ class BoostingEngine:
             ).astype(np.int32),
         )
 
-        if n_local < self.dtrain.n_rows:
+        if row_finish:
+            # one row-order walk of the finished tree over the binned
+            # matrix: each row lands in the leaf the partition chose (or,
+            # on the last level, would have chosen) and takes the same
+            # single f32 add of the same float32(eta * w). Covers the
+            # sampled and the unsampled rows alike.
+            ops.apply_tree_binned(
+                self.dtrain.bins,
+                self.margin if self.n_class == 1 else self.margin[:, cls],
+                tree.feat, ta.split_bin[:n], tree.left, tree.default_left,
+                tree.value,
+            )
+        elif n_local < self.dtrain.n_rows:
             # row sampling: EVERY row's margin must advance (xgboost
             # UpdatePredictionCache semantics) - the leaf-segment
             # scatter only covers the sampled rows, which left

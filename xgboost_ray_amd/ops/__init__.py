@@ -54,6 +54,28 @@ def quantize_gpair(gpair: torch.Tensor, scale_g: float, scale_h: float) -> torch
     return _impl(gpair).quantize_gpair(gpair, scale_g, scale_h)
 
 
+def quantize_gpair_sums(gpair, scale_g, scale_h):
+    """GPU only: ``quantize_gpair`` that also returns the int64 [2] column
+    sums of its output (== ``gq.sum(0, dtype=int64)``, integer and so
+    order-free) from the same pass over the data."""
+    return _gpu().quantize_gpair(gpair, scale_g, scale_h, return_sums=True)
+
+
+def apply_tree_binned(bins, margin, feat, split_bin, left, default_left,
+                      value):
+    """GPU only: add one tree's leaf values into ``margin`` in row order.
+
+    Every row of ``bins`` (uint8 [n, F], any row stride) walks the tree:
+    at a split node go left iff ``bin <= split_bin`` (missing bin 255
+    follows ``default_left``), right child = left + 1; at the leaf
+    ``margin[row] += value[leaf]`` (one f32 add). ``feat < 0`` marks a
+    leaf; the tree arrays live on the host. ``margin`` is an f32 vector or
+    a strided column view of a [n, C] matrix, updated in place.
+    """
+    return _gpu().apply_tree_binned(
+        bins, margin, feat, split_bin, left, default_left, value)
+
+
 def bin_matrix(values, cuts_flat, cut_ptr):
     """fp32 [n, F] feature matrix -> uint8 [n, F] bin indices.
 

@@ -33,8 +33,30 @@ def _load():
     return _ext
 
 
-def quantize_gpair(gpair, scale_g, scale_h):
+def quantize_gpair(gpair, scale_g, scale_h, return_sums=False):
+    if return_sums:
+        # (gq, int64 [2] device == gq.sum(0)) from the one quantize pass
+        gq, sums = _load().quantize_gpair_sums(
+            gpair.contiguous(), scale_g, scale_h)
+        return gq, sums
     return _load().quantize_gpair(gpair.contiguous(), scale_g, scale_h)
+
+
+def apply_tree_binned(bins, margin, feat, split_bin, left, default_left,
+                      value):
+    """margin[r] += value[leaf(r)], the leaf found by walking the tree over
+    row r's bin bytes. Tree arrays are host numpy/torch vectors (feat < 0
+    marks a leaf); ``margin`` may be a strided column view (updated in
+    place, no contiguous round trip)."""
+    _load().apply_tree_binned(
+        bins, margin,
+        torch.as_tensor(feat, dtype=torch.int32),
+        torch.as_tensor(split_bin, dtype=torch.int32),
+        torch.as_tensor(left, dtype=torch.int32),
+        torch.as_tensor(default_left, dtype=torch.uint8),
+        torch.as_tensor(value, dtype=torch.float32),
+    )
+    return margin
 
 
 def bin_matrix(values, cuts_flat, cut_ptr):

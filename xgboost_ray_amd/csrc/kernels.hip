@@ -672,7 +672,13 @@ __device__ inline double calc_weight_d(double G, double H, double lam,
 }
 
 __global__ __launch_bounds__(256) void find_splits_kf_kernel(
-    const long long* __restrict__ hist,  // [K, F, B, 2]
+    long long* hist,  // [K, F, B, 2]; rows >= K_built written when deriving
+    // sibling derivation (prev_hist == nullptr: off): scan slot
+    // k >= K_built is parent - built sibling,
+    // hist[k] = prev_hist[pslots[k-K_built]] - hist[spos[k-K_built]]
+    const long long* __restrict__ prev_hist,  // [K_prev, F, B, 2] or null
+    const int64_t* __restrict__ pslots, const int64_t* __restrict__ spos,
+    int K_built,
     const long long* __restrict__ parent_g, const long long* __restrict__ parent_h,
     const int32_t* __restrict__ feat_bins, double scale_g, double scale_h,
     double lam, double alpha, double gamma, double mcw,
@@ -701,6 +707,45 @@ __global__ __launch_bounds__(256) void find_splits_kf_kernel(
   if (kf >= (int64_t)K * F) return;
   const int k = (int)(kf / F);
   const int f = (int)(kf % F);
+  const int bpl = (B + WAVE - 1) / WAVE;  // <= 4 for B <= 256
+  // this lane's contiguous bin chunk, loaded once; a derived row is
+  // parent - sibling, stored for the next depth (ALL B bins, and before
+  // any early return: the next depth reads the row as its parent even
+  // when this (node, feature) is gated off) and scanned from registers.
+  // Integer subtraction is exact, so the scan sees the same int64 values
+  // as a separately materialized difference.
+  long long vg[4], vh[4];
+  {
+    const size_t row = (size_t)F * B * 2;
+    const size_t fo = (size_t)f * B * 2;
+    const bool derive = prev_hist != nullptr && k >= K_built;
+    const longlong2* src = (const longlong2*)(hist + (size_t)k * row + fo);
+    const longlong2* par = nullptr;
+    longlong2* dst = nullptr;
+    if (derive) {
+      const int j = k - K_built;
+      par = (const longlong2*)(prev_hist + (size_t)pslots[j] * row + fo);
+      src = (const longlong2*)(hist + (size_t)spos[j] * row + fo);
+      dst = (longlong2*)(hist + (size_t)k * row + fo);
+    }
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      vg[j] = 0;
+      vh[j] = 0;
+      const int b = lane * bpl + j;
+      if (j < bpl && b < B) {
+        longlong2 v = src[b];
+        if (derive) {
+          const longlong2 p = par[b];
+          v.x = p.x - v.x;
+          v.y = p.y - v.y;
+          dst[b] = v;
+        }
+        vg[j] = v.x;
+        vh[j] = v.y;
+      }
+    }
+  }
   if (allowed != nullptr && allowed[kf] == 0) {
     // interaction constraints: disallowed (node, feature) -> the same
     // no-split sentinel the CPU oracle produces (gain -1, dl 0)
@@ -715,21 +760,16 @@ __global__ __launch_bounds__(256) void find_splits_kf_kernel(
   }
   const double inv_g = 1.0 / scale_g;
   const double inv_h = 1.0 / scale_h;
-  const long long* gh = hist + ((size_t)k * F + f) * B * 2;
   const int nb = feat_bins[f];
 
   // lane-local inclusive prefixes over this lane's contiguous bin chunk
-  const int bpl = (B + WAVE - 1) / WAVE;  // <= 4 for B <= 256
   long long lpg[4], lph[4];
   long long gsum = 0, hsum = 0;
   #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (j < bpl) {
-      const int b = lane * bpl + j;
-      if (b < B) {
-        gsum += gh[b * 2];
-        hsum += gh[b * 2 + 1];
-      }
+      gsum += vg[j];
+      hsum += vh[j];
       lpg[j] = gsum;
       lph[j] = hsum;
     }
@@ -1025,6 +1065,58 @@ __global__ void partition_prefix_kernel(
       left_before[base + threadIdx.x] = run + src[threadIdx.x] - v;
     run += src[255];
     __syncthreads();
+  }
+  if (threadIdx.x == 0) node_left_total[k] = run;
+}
+
+// Same outputs from a wave shuffle scan: each of the 4 waves scans its 64
+// chunk counts with __shfl_up, one 4-entry LDS step carries the wave
+// totals across - two barriers per 256 chunks instead of nine. Workgroups
+// past the split-node count write a 0 left total, so the caller needs no
+// zero fill of node_left_total. int64 throughout, like the LDS version.
+__global__ __launch_bounds__(PART_THREADS) void partition_prefix_shfl_kernel(
+    const int32_t* __restrict__ block_counts,  // [total_chunks]
+    const int64_t* __restrict__ meta,          // layout as count kernel
+    const int64_t* __restrict__ limits,        // nullptr or [2]
+    int64_t* __restrict__ left_before,         // [total_chunks]
+    int64_t* __restrict__ node_left_total,     // [K]
+    int K) {
+  const int k = blockIdx.x;
+  int64_t Ks = K;
+  if (limits != nullptr) Ks = limits[0];
+  if (k >= Ks) {
+    if (threadIdx.x == 0 && k < K) node_left_total[k] = 0;
+    return;
+  }
+  const int64_t* chunk_off = meta + 2 * Ks;
+  const int64_t c0 = chunk_off[k], c1 = chunk_off[k + 1];
+  __shared__ int64_t wave_tot[PART_WAVES];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave_id = threadIdx.x / WAVE;
+  int64_t run = 0;
+  for (int64_t base = c0; base < c1; base += PART_THREADS) {
+    const int nin = (int)min((int64_t)PART_THREADS, c1 - base);
+    const int64_t v =
+        (int)threadIdx.x < nin ? (int64_t)block_counts[base + threadIdx.x] : 0;
+    long long incl = v;
+    #pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+      const long long u = __shfl_up(incl, d, WAVE);
+      if (lane >= d) incl += u;
+    }
+    if (lane == WAVE - 1) wave_tot[wave_id] = incl;
+    __syncthreads();
+    int64_t woff = 0, tot = 0;
+    #pragma unroll
+    for (int w = 0; w < PART_WAVES; ++w) {
+      const int64_t t = wave_tot[w];
+      if (w < wave_id) woff += t;
+      tot += t;
+    }
+    if ((int)threadIdx.x < nin)
+      left_before[base + threadIdx.x] = run + woff + incl - v;
+    run += tot;
+    __syncthreads();  // wave_tot is rewritten by the next block of chunks
   }
   if (threadIdx.x == 0) node_left_total[k] = run;
 }
@@ -1880,17 +1972,53 @@ torch::Tensor build_histogram(torch::Tensor bins, torch::Tensor gpair_q,
   return hist;
 }
 
-std::vector<torch::Tensor> find_splits(torch::Tensor hist, torch::Tensor parent_g,
-                                       torch::Tensor parent_h,
-                                       torch::Tensor feat_bins, double scale_g,
-                                       double scale_h, double lam, double alpha,
-                                       double gamma, double mcw,
-                                       torch::Tensor mono, torch::Tensor bounds,
-                                       torch::Tensor allowed, bool pull) {
+using OptTensor = c10::optional<torch::Tensor>;
+
+// The (node, feature) scan: launches find_splits_kf_kernel and returns
+// {kf_gain, kf_bin, kf_dl, kf_lg, kf_lh}, each [K*F]. With prev_hist /
+// pslots[nd] / spos[nd] given, the last nd rows of hist are derived
+// in-kernel as prev_hist[pslots] - hist[spos] (spos < K - nd) and stored.
+std::vector<torch::Tensor> find_splits_kf(
+    torch::Tensor hist, torch::Tensor parent_g, torch::Tensor parent_h,
+    torch::Tensor feat_bins, double scale_g, double scale_h, double lam,
+    double alpha, double gamma, double mcw, torch::Tensor mono,
+    torch::Tensor bounds, torch::Tensor allowed, OptTensor prev_hist,
+    OptTensor pslots, OptTensor spos) {
   const int K = (int)hist.size(0);
   const int F = (int)hist.size(1);
   const int B = (int)hist.size(2);
   auto dev = hist.device();
+  const long long* prev_p = nullptr;
+  const int64_t* pslots_p = nullptr;
+  const int64_t* spos_p = nullptr;
+  int K_built = K;
+  if (prev_hist.has_value() && pslots.has_value() && pslots->numel() > 0) {
+    TORCH_CHECK(spos.has_value() && spos->numel() == pslots->numel(),
+                "find_splits: pslots and spos must have equal length");
+    const int64_t nd = pslots->numel();
+    TORCH_CHECK(nd <= K, "find_splits: more derived rows than scan slots");
+    TORCH_CHECK(hist.is_contiguous() && prev_hist->is_contiguous() &&
+                    prev_hist->dim() == 4 && prev_hist->size(1) == F &&
+                    prev_hist->size(2) == B &&
+                    prev_hist->scalar_type() == torch::kInt64,
+                "find_splits: prev_hist must be contiguous int64 [*, F, B, 2]");
+    TORCH_CHECK(on_gpu(*pslots) && on_gpu(*spos) &&
+                    pslots->scalar_type() == torch::kInt64 &&
+                    spos->scalar_type() == torch::kInt64 &&
+                    pslots->is_contiguous() && spos->is_contiguous(),
+                "find_splits: pslots/spos must be contiguous device int64");
+    TORCH_CHECK(prev_hist->data_ptr() != hist.data_ptr(),
+                "find_splits: prev_hist must not alias hist");
+    prev_p = reinterpret_cast<const long long*>(prev_hist->data_ptr<int64_t>());
+    pslots_p = pslots->data_ptr<int64_t>();
+    spos_p = spos->data_ptr<int64_t>();
+    K_built = K - (int)nd;
+  }
+  TORCH_CHECK(hist.is_contiguous() && hist.size(3) == 2 &&
+                  reinterpret_cast<uintptr_t>(hist.data_ptr()) % 16 == 0 &&
+                  (prev_p == nullptr ||
+                   reinterpret_cast<uintptr_t>(prev_p) % 16 == 0),
+              "find_splits: hist must be contiguous [K, F, B, 2], 16B-aligned");
   auto optsd = torch::TensorOptions().dtype(torch::kFloat64).device(dev);
   auto optsi = torch::TensorOptions().dtype(torch::kInt32).device(dev);
   auto optsl = torch::TensorOptions().dtype(torch::kInt64).device(dev);
@@ -1900,15 +2028,17 @@ std::vector<torch::Tensor> find_splits(torch::Tensor hist, torch::Tensor parent_
   auto kf_dl = torch::empty({(int64_t)K * F}, optsb);
   auto kf_lg = torch::empty({(int64_t)K * F}, optsl);
   auto kf_lh = torch::empty({(int64_t)K * F}, optsl);
-  auto stream = c10::hip::getCurrentHIPStream();
   int64_t total = (int64_t)K * F;
+  if (total == 0) return {kf_gain, kf_bin, kf_dl, kf_lg, kf_lh};
+  auto stream = c10::hip::getCurrentHIPStream();
   // one 64-lane wave per (k, f), four waves per 256-thread block; no LDS
   const int waves_per_block = 4;
   hipLaunchKernelGGL(find_splits_kf_kernel,
                      dim3((uint32_t)ceil_div(total, waves_per_block)),
                      dim3(waves_per_block * WAVE), 0,
                      stream.stream(),
-                     reinterpret_cast<const long long*>(hist.data_ptr<int64_t>()),
+                     reinterpret_cast<long long*>(hist.data_ptr<int64_t>()),
+                     prev_p, pslots_p, spos_p, K_built,
                      reinterpret_cast<const long long*>(parent_g.data_ptr<int64_t>()),
                      reinterpret_cast<const long long*>(parent_h.data_ptr<int64_t>()),
                      feat_bins.data_ptr<int32_t>(), scale_g, scale_h, lam,
@@ -1920,14 +2050,39 @@ std::vector<torch::Tensor> find_splits(torch::Tensor hist, torch::Tensor parent_
                      kf_bin.data_ptr<int32_t>(), kf_dl.data_ptr<uint8_t>(),
                      reinterpret_cast<long long*>(kf_lg.data_ptr<int64_t>()),
                      reinterpret_cast<long long*>(kf_lh.data_ptr<int64_t>()), K, F, B);
-  auto out_packed = torch::empty({K, 6}, optsl);
+  return {kf_gain, kf_bin, kf_dl, kf_lg, kf_lh};
+}
+
+static void launch_reduce(const std::vector<torch::Tensor>& kf,
+                          torch::Tensor out_packed, int K, int F) {
+  if (K == 0) return;
+  auto stream = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(find_splits_reduce_kernel, dim3((uint32_t)ceil_div(K, 64)),
-                     dim3(64), 0, stream.stream(), kf_gain.data_ptr<double>(),
-                     kf_bin.data_ptr<int32_t>(), kf_dl.data_ptr<uint8_t>(),
-                     reinterpret_cast<const long long*>(kf_lg.data_ptr<int64_t>()),
-                     reinterpret_cast<const long long*>(kf_lh.data_ptr<int64_t>()),
+                     dim3(64), 0, stream.stream(), kf[0].data_ptr<double>(),
+                     kf[1].data_ptr<int32_t>(), kf[2].data_ptr<uint8_t>(),
+                     reinterpret_cast<const long long*>(kf[3].data_ptr<int64_t>()),
+                     reinterpret_cast<const long long*>(kf[4].data_ptr<int64_t>()),
                      reinterpret_cast<long long*>(out_packed.data_ptr<int64_t>()),
                      K, F);
+}
+
+std::vector<torch::Tensor> find_splits(torch::Tensor hist, torch::Tensor parent_g,
+                                       torch::Tensor parent_h,
+                                       torch::Tensor feat_bins, double scale_g,
+                                       double scale_h, double lam, double alpha,
+                                       double gamma, double mcw,
+                                       torch::Tensor mono, torch::Tensor bounds,
+                                       torch::Tensor allowed, bool pull,
+                                       OptTensor prev_hist, OptTensor pslots,
+                                       OptTensor spos) {
+  const int K = (int)hist.size(0);
+  const int F = (int)hist.size(1);
+  auto kf = find_splits_kf(hist, parent_g, parent_h, feat_bins, scale_g,
+                           scale_h, lam, alpha, gamma, mcw, mono, bounds,
+                           allowed, prev_hist, pslots, spos);
+  auto out_packed = torch::empty(
+      {K, 6}, torch::TensorOptions().dtype(torch::kInt64).device(hist.device()));
+  launch_reduce(kf, out_packed, K, F);
   if (!pull) return {out_packed};  // device [K,6]: consumed by the
                                    // fused partition (single-sync path)
   // pinned D2H: the caller consumes (copies out of) the result
@@ -2024,14 +2179,256 @@ __global__ __launch_bounds__(1024) void plan_partition_kernel(
   }
 }
 
-// Fused scan-consume partition: find_splits' packed output feeds the
-// partition directly on device; the host gets {packed | left_counts}
-// in ONE pinned D2H it reads after a single stream sync per depth
-// (replacing the 2 syncs/depth of the host-planned path).
-std::vector<torch::Tensor> partition_rows_from_packed(
-    torch::Tensor bins, torch::Tensor ridx, torch::Tensor starts_ord,
-    torch::Tensor counts_ord, torch::Tensor packed, torch::Tensor gseg,
-    torch::Tensor bins_t, int64_t chunk_bound, torch::Tensor ridx_dest) {
+// find_splits_reduce_kernel + plan_partition_kernel as ONE single-
+// workgroup kernel for K <= 1024 (between them the two launches were a
+// serial thread walking F features twice and a 20-barrier block scan).
+// Reduce: wave w takes nodes w, w+16, ...; lanes cover the features and
+// keep a dl=1 and a dl=0 candidate each (strictly-greater replacement in
+// ascending feature order == lowest feature wins ties, start gain -1, a
+// NaN gain never compares greater); a butterfly merges the lanes by
+// (gain desc, feature asc) - the order the serial loop realizes - and
+// the dl=0 winner replaces the dl=1 winner only on strictly greater
+// gain. Plan: thread k owns node k (what plan_partition_kernel does at
+// K <= 1024), reading the reduce phase's results from LDS; the block
+// scan is a wave shuffle scan plus a 16-entry carry.
+#define RP_THREADS 1024
+#define RP_WAVES (RP_THREADS / WAVE)
+__global__ __launch_bounds__(RP_THREADS) void reduce_plan_kernel(
+    const double* __restrict__ kf_gain, const int32_t* __restrict__ kf_bin,
+    const uint8_t* __restrict__ kf_dl, const long long* __restrict__ kf_lg,
+    const long long* __restrict__ kf_lh,
+    const int64_t* __restrict__ starts_ord,  // [K] scan-slot order
+    const int64_t* __restrict__ counts_ord,  // [K]
+    long long* __restrict__ out_packed,      // [K, 6]
+    int64_t* __restrict__ meta,     // [6K+1] compacted partition meta
+    int64_t* __restrict__ scalars,  // [2]: n_split, total_chunks
+    int K, int F) {
+  __shared__ int s_gbits[RP_THREADS];
+  __shared__ int s_feat[RP_THREADS];
+  __shared__ int s_bin[RP_THREADS];
+  __shared__ int s_dl[RP_THREADS];
+  __shared__ long long s_wok[RP_WAVES];
+  __shared__ long long s_wch[RP_WAVES];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave_id = threadIdx.x / WAVE;
+
+  for (int k = wave_id; k < K; k += RP_WAVES) {
+    double g1 = -1.0, g0 = -1.0;
+    int f1 = -1, f0 = -1;
+    for (int f = lane; f < F; f += WAVE) {
+      const int64_t kf = (int64_t)k * F + f;
+      const int dl = (int)kf_dl[kf];
+      const double g = kf_gain[kf];
+      if (dl == 1) {
+        if (g > g1) { g1 = g; f1 = f; }
+      } else if (dl == 0) {
+        if (g > g0) { g0 = g; f0 = f; }
+      }
+    }
+    #pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+      const double og1 = __shfl_xor(g1, off, WAVE);
+      const int of1 = __shfl_xor(f1, off, WAVE);
+      const double og0 = __shfl_xor(g0, off, WAVE);
+      const int of0 = __shfl_xor(f0, off, WAVE);
+      // equal gains with a candidate on both sides: lowest feature (an
+      // empty side has gain -1, which a held candidate always exceeds)
+      if (og1 > g1 || (og1 == g1 && of1 >= 0 && of1 < f1)) { g1 = og1; f1 = of1; }
+      if (og0 > g0 || (og0 == g0 && of0 >= 0 && of0 < f0)) { g0 = og0; f0 = of0; }
+    }
+    if (lane == 0) {
+      double bg = g1;
+      int bf = f1, bdl = f1 >= 0 ? 1 : 0;
+      if (g0 > bg) { bg = g0; bf = f0; bdl = 0; }
+      int bb = 0;
+      long long blg = 0, blh = 0;
+      if (bf >= 0) {
+        const int64_t kf = (int64_t)k * F + bf;
+        bb = kf_bin[kf];
+        blg = kf_lg[kf];
+        blh = kf_lh[kf];
+      }
+      const int gbits = __float_as_int((float)bg);
+      long long* row = out_packed + (size_t)k * 6;
+      row[0] = (long long)gbits;
+      row[1] = bf;
+      row[2] = bb;
+      row[3] = bdl;
+      row[4] = blg;
+      row[5] = blh;
+      s_gbits[k] = gbits;
+      s_feat[k] = bf;
+      s_bin[k] = bb;
+      s_dl[k] = bdl;
+    }
+  }
+  __syncthreads();
+
+  const int k = threadIdx.x;
+  bool ok = false;
+  long long cnt = 0, ch = 0;
+  if (k < K) {
+    const float gain = __int_as_float(s_gbits[k]);
+    ok = (gain > 0.0f) && (s_feat[k] >= 0) && isfinite(gain);
+    if (ok) {
+      cnt = counts_ord[k];
+      ch = (cnt + PART_CHUNK - 1) / PART_CHUNK;
+    }
+  }
+  long long iok = ok ? 1 : 0, ich = ch;  // inclusive wave scans
+  #pragma unroll
+  for (int d = 1; d < WAVE; d <<= 1) {
+    const long long uo = __shfl_up(iok, d, WAVE);
+    const long long uc = __shfl_up(ich, d, WAVE);
+    if (lane >= d) {
+      iok += uo;
+      ich += uc;
+    }
+  }
+  if (lane == WAVE - 1) {
+    s_wok[wave_id] = iok;
+    s_wch[wave_id] = ich;
+  }
+  __syncthreads();
+  long long ok_off = 0, ch_off = 0, n_split = 0, total_chunks = 0;
+  #pragma unroll
+  for (int w = 0; w < RP_WAVES; ++w) {
+    const long long a = s_wok[w], b = s_wch[w];
+    if (w < wave_id) {
+      ok_off += a;
+      ch_off += b;
+    }
+    n_split += a;
+    total_chunks += b;
+  }
+  // meta layout: see plan_partition_kernel
+  if (ok) {
+    const long long pos = ok_off + iok - 1;
+    meta[pos] = starts_ord[k];
+    meta[n_split + pos] = cnt;
+    meta[2 * n_split + pos] = ch_off + ich - ch;
+    meta[3 * n_split + 1 + pos] = s_feat[k];
+    meta[4 * n_split + 1 + pos] = s_bin[k];
+    meta[5 * n_split + 1 + pos] = s_dl[k];
+  }
+  if (threadIdx.x == 0) {
+    meta[3 * n_split] = total_chunks;
+    scalars[0] = n_split;
+    scalars[1] = total_chunks;
+  }
+}
+
+static void launch_plan(torch::Tensor packed, torch::Tensor starts_ord,
+                        torch::Tensor counts_ord, torch::Tensor meta,
+                        torch::Tensor scalars, int K) {
+  auto stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(plan_partition_kernel, dim3(1), dim3(1024), 0,
+                     stream.stream(),
+                     reinterpret_cast<const long long*>(packed.data_ptr<int64_t>()),
+                     starts_ord.data_ptr<int64_t>(),
+                     counts_ord.data_ptr<int64_t>(),
+                     meta.data_ptr<int64_t>(), scalars.data_ptr<int64_t>(),
+                     K);
+}
+
+static void check_kf(const std::vector<torch::Tensor>& kf,
+                     const torch::Tensor& starts_ord,
+                     const torch::Tensor& counts_ord, int* K, int* F) {
+  TORCH_CHECK(kf.size() == 5, "expected kf_gain, kf_bin, kf_dl, kf_lg, kf_lh");
+  *K = (int)starts_ord.numel();
+  TORCH_CHECK(*K > 0 && counts_ord.numel() == *K,
+              "starts_ord/counts_ord must be non-empty, equal length");
+  const int64_t KF = kf[0].numel();
+  TORCH_CHECK(KF > 0 && KF % *K == 0, "kf arrays must hold K*F entries");
+  *F = (int)(KF / *K);
+  TORCH_CHECK(kf[0].scalar_type() == torch::kFloat64 &&
+                  kf[1].scalar_type() == torch::kInt32 &&
+                  kf[2].scalar_type() == torch::kUInt8 &&
+                  kf[3].scalar_type() == torch::kInt64 &&
+                  kf[4].scalar_type() == torch::kInt64 &&
+                  starts_ord.scalar_type() == torch::kInt64 &&
+                  counts_ord.scalar_type() == torch::kInt64,
+              "reduce+plan: wrong dtype");
+  for (const auto& t : kf)
+    TORCH_CHECK(on_gpu(t) && t.is_contiguous() && t.numel() == KF,
+                "kf arrays must be contiguous device tensors of K*F entries");
+  TORCH_CHECK(on_gpu(starts_ord) && on_gpu(counts_ord) &&
+                  starts_ord.is_contiguous() && counts_ord.is_contiguous(),
+              "starts_ord/counts_ord must be contiguous device tensors");
+}
+
+// Per-node best split + partition plan from the (node, feature) scan
+// results. Fused: ONE single-workgroup kernel at K <= 1024 (above that
+// the two legacy kernels), into a [7K] device buffer whose first 6K
+// entries are `packed` and whose last K the partition fills with the
+// left totals - the layout the host pulls in one copy. Returns
+// {packed, meta, scalars, pullbuf}.
+static std::vector<torch::Tensor> reduce_plan_impl(
+    const std::vector<torch::Tensor>& kf, torch::Tensor starts_ord,
+    torch::Tensor counts_ord, bool fused) {
+  int K = 0, F = 0;
+  check_kf(kf, starts_ord, counts_ord, &K, &F);
+  auto optsl =
+      torch::TensorOptions().dtype(torch::kInt64).device(kf[0].device());
+  auto meta = torch::empty({6 * (int64_t)K + 2}, optsl);
+  if (!fused) {
+    auto packed = torch::empty({K, 6}, optsl);
+    auto scalars = torch::zeros({2}, optsl);
+    launch_reduce(kf, packed, K, F);
+    launch_plan(packed, starts_ord, counts_ord, meta, scalars, K);
+    return {packed, meta, scalars, torch::Tensor()};
+  }
+  auto pullbuf = torch::empty({7 * (int64_t)K}, optsl);
+  auto packed = pullbuf.narrow(0, 0, 6 * (int64_t)K).view({K, 6});
+  auto scalars = torch::empty({2}, optsl);  // both written by the kernel
+  if (K <= RP_THREADS) {
+    auto stream = c10::hip::getCurrentHIPStream();
+    hipLaunchKernelGGL(reduce_plan_kernel, dim3(1), dim3(RP_THREADS), 0,
+                       stream.stream(), kf[0].data_ptr<double>(),
+                       kf[1].data_ptr<int32_t>(), kf[2].data_ptr<uint8_t>(),
+                       reinterpret_cast<const long long*>(kf[3].data_ptr<int64_t>()),
+                       reinterpret_cast<const long long*>(kf[4].data_ptr<int64_t>()),
+                       starts_ord.data_ptr<int64_t>(),
+                       counts_ord.data_ptr<int64_t>(),
+                       reinterpret_cast<long long*>(packed.data_ptr<int64_t>()),
+                       meta.data_ptr<int64_t>(), scalars.data_ptr<int64_t>(),
+                       K, F);
+  } else {
+    launch_reduce(kf, packed, K, F);
+    launch_plan(packed, starts_ord, counts_ord, meta, scalars, K);
+  }
+  return {packed, meta, scalars, pullbuf};
+}
+
+std::vector<torch::Tensor> reduce_plan_fused(
+    torch::Tensor kf_gain, torch::Tensor kf_bin, torch::Tensor kf_dl,
+    torch::Tensor kf_lg, torch::Tensor kf_lh, torch::Tensor starts_ord,
+    torch::Tensor counts_ord) {
+  auto r = reduce_plan_impl({kf_gain, kf_bin, kf_dl, kf_lg, kf_lh},
+                            starts_ord, counts_ord, /*fused=*/true);
+  return {r[0], r[1], r[2]};
+}
+
+std::vector<torch::Tensor> reduce_plan_legacy(
+    torch::Tensor kf_gain, torch::Tensor kf_bin, torch::Tensor kf_dl,
+    torch::Tensor kf_lg, torch::Tensor kf_lh, torch::Tensor starts_ord,
+    torch::Tensor counts_ord) {
+  auto r = reduce_plan_impl({kf_gain, kf_bin, kf_dl, kf_lg, kf_lh},
+                            starts_ord, counts_ord, /*fused=*/false);
+  return {r[0], r[1], r[2]};
+}
+
+// count + prefix + pull of a device-planned partition (everything but
+// the plan before it and the scatter after it). `pullbuf` ([7K], packed
+// in its first 6K) defined: the left totals land in its tail and ONE
+// D2H brings both to the host; undefined: two copies. `fused` selects
+// the shuffle-scan prefix kernel, which zeroes the unused left totals
+// itself (no fill). Returns the list partition_rows_from_packed returns.
+static std::vector<torch::Tensor> partition_planned(
+    torch::Tensor bins, torch::Tensor ridx, torch::Tensor packed,
+    torch::Tensor meta, torch::Tensor scalars, torch::Tensor pullbuf,
+    torch::Tensor gseg, torch::Tensor bins_t, int64_t chunk_bound,
+    torch::Tensor ridx_dest, bool fused) {
   const int K = (int)packed.size(0);     // frontier bound (scan-slot count)
   auto dev = bins.device();
   // ping-pong destination: the caller tracks which buffer each leaf
@@ -2045,16 +2442,7 @@ std::vector<torch::Tensor> partition_rows_from_packed(
   // the clone). Saves an 88 MB device copy per depth at 11M rows.
   auto gseg_out = torch::empty_like(gseg);
   auto optsl = torch::TensorOptions().dtype(torch::kInt64).device(dev);
-  auto meta = torch::empty({6 * (int64_t)K + 2}, optsl);
-  auto scalars = torch::zeros({2}, optsl);
   auto stream = c10::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(plan_partition_kernel, dim3(1), dim3(1024), 0,
-                     stream.stream(),
-                     reinterpret_cast<const long long*>(packed.data_ptr<int64_t>()),
-                     starts_ord.data_ptr<int64_t>(),
-                     counts_ord.data_ptr<int64_t>(),
-                     meta.data_ptr<int64_t>(), scalars.data_ptr<int64_t>(),
-                     K);
   int64_t* mp = meta.data_ptr<int64_t>();
   const int64_t* sc2 = scalars.data_ptr<int64_t>();
   auto block_counts = torch::empty({std::max<int64_t>(chunk_bound, 1)},
@@ -2072,13 +2460,27 @@ std::vector<torch::Tensor> partition_rows_from_packed(
                      bins_t.numel() ? bins_t.data_ptr<uint8_t>() : nullptr,
                      bins.size(0));
   auto left_before = torch::empty({std::max<int64_t>(chunk_bound, 1)}, optsl);
-  auto node_left_total = torch::zeros({K}, optsl);
-  hipLaunchKernelGGL(partition_prefix_kernel,
-                     dim3((uint32_t)std::max(K, 1)), dim3(256), 0,
-                     stream.stream(),
-                     block_counts.data_ptr<int32_t>(), mp, sc2,
-                     left_before.data_ptr<int64_t>(),
-                     node_left_total.data_ptr<int64_t>(), K);
+  torch::Tensor node_left_total;
+  if (pullbuf.defined())
+    node_left_total = pullbuf.narrow(0, 6 * (int64_t)K, K);
+  else
+    node_left_total = fused ? torch::empty({K}, optsl)
+                            : torch::zeros({K}, optsl);
+  if (fused) {
+    hipLaunchKernelGGL(partition_prefix_shfl_kernel,
+                       dim3((uint32_t)std::max(K, 1)), dim3(PART_THREADS), 0,
+                       stream.stream(),
+                       block_counts.data_ptr<int32_t>(), mp, sc2,
+                       left_before.data_ptr<int64_t>(),
+                       node_left_total.data_ptr<int64_t>(), K);
+  } else {
+    hipLaunchKernelGGL(partition_prefix_kernel,
+                       dim3((uint32_t)std::max(K, 1)), dim3(256), 0,
+                       stream.stream(),
+                       block_counts.data_ptr<int32_t>(), mp, sc2,
+                       left_before.data_ptr<int64_t>(),
+                       node_left_total.data_ptr<int64_t>(), K);
+  }
   // ONE async pinned D2H of everything the host replay needs -
   // enqueued BEFORE the scatter, so the host's single sync wakes as
   // soon as scan+plan+count+prefix are done and ALL its bookkeeping
@@ -2087,26 +2489,66 @@ std::vector<torch::Tensor> partition_rows_from_packed(
   // than the 2-sync structure)
   static thread_local PinnedStager pull_stager;
   auto pull = pull_stager.get(7 * (int64_t)K);
-  pull.narrow(0, 0, 6 * (int64_t)K)
-      .copy_(packed.view({-1}), /*non_blocking=*/true);
-  pull.narrow(0, 6 * (int64_t)K, K)
-      .copy_(node_left_total, /*non_blocking=*/true);
+  if (pullbuf.defined()) {
+    pull.copy_(pullbuf, /*non_blocking=*/true);
+  } else {
+    pull.narrow(0, 0, 6 * (int64_t)K)
+        .copy_(packed.view({-1}), /*non_blocking=*/true);
+    pull.narrow(0, 6 * (int64_t)K, K)
+        .copy_(node_left_total, /*non_blocking=*/true);
+  }
   pull_stager.mark(stream.stream());
   auto cb = torch::full({1}, chunk_bound, torch::kInt64);
   return {ridx_out, gseg_out, pull, meta, scalars, left_before,
           node_left_total, flags, cb};
 }
 
+// Fused scan-consume partition: find_splits' packed output feeds the
+// partition directly on device; the host gets {packed | left_counts}
+// in a pinned D2H it reads after a single stream sync per depth
+// (replacing the 2 syncs/depth of the host-planned path). fused_glue
+// drops the two zero fills and takes the shuffle-scan prefix kernel.
+std::vector<torch::Tensor> partition_rows_from_packed(
+    torch::Tensor bins, torch::Tensor ridx, torch::Tensor starts_ord,
+    torch::Tensor counts_ord, torch::Tensor packed, torch::Tensor gseg,
+    torch::Tensor bins_t, int64_t chunk_bound, torch::Tensor ridx_dest,
+    bool fused_glue) {
+  const int K = (int)packed.size(0);
+  auto optsl =
+      torch::TensorOptions().dtype(torch::kInt64).device(bins.device());
+  auto meta = torch::empty({6 * (int64_t)K + 2}, optsl);
+  // the plan kernel writes both scalars
+  auto scalars = fused_glue ? torch::empty({2}, optsl)
+                            : torch::zeros({2}, optsl);
+  launch_plan(packed, starts_ord, counts_ord, meta, scalars, K);
+  return partition_planned(bins, ridx, packed, meta, scalars,
+                           torch::Tensor(), gseg, bins_t, chunk_bound,
+                           ridx_dest, fused_glue);
+}
+
+// The same partition fed by the (node, feature) scan results of
+// find_splits_kf: reduce + plan in one kernel, no fills, one pull.
+std::vector<torch::Tensor> partition_rows_from_kf(
+    torch::Tensor bins, torch::Tensor ridx, torch::Tensor starts_ord,
+    torch::Tensor counts_ord, torch::Tensor kf_gain, torch::Tensor kf_bin,
+    torch::Tensor kf_dl, torch::Tensor kf_lg, torch::Tensor kf_lh,
+    torch::Tensor gseg, torch::Tensor bins_t, int64_t chunk_bound,
+    torch::Tensor ridx_dest) {
+  auto r = reduce_plan_impl({kf_gain, kf_bin, kf_dl, kf_lg, kf_lh},
+                            starts_ord, counts_ord, /*fused=*/true);
+  return partition_planned(bins, ridx, r[0], r[1], r[2], r[3], gseg, bins_t,
+                           chunk_bound, ridx_dest, /*fused=*/true);
+}
+
 // Scatter phase of the device-planned partition: launched AFTER the
 // caller records its pull event, so the host's event-wait wakes before
 // the scatter and all bookkeeping overlaps it.
-void partition_scatter_from_packed(
+void partition_scatter_planned(
     torch::Tensor ridx, torch::Tensor ridx_out, torch::Tensor gseg,
     torch::Tensor gseg_out, torch::Tensor meta, torch::Tensor scalars,
     torch::Tensor left_before, torch::Tensor node_left_total,
-    torch::Tensor flags, torch::Tensor cb) {
+    torch::Tensor flags, int64_t chunk_bound) {
   const int K = (int)node_left_total.size(0);
-  const int64_t chunk_bound = cb.item<int64_t>();
   auto stream = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(partition_scatter_kernel,
                      dim3((uint32_t)std::max<int64_t>(chunk_bound, 1)),
@@ -2120,6 +2562,16 @@ void partition_scatter_from_packed(
                      meta.data_ptr<int64_t>(), scalars.data_ptr<int64_t>(),
                      left_before.data_ptr<int64_t>(),
                      node_left_total.data_ptr<int64_t>(), K);
+}
+
+void partition_scatter_from_packed(
+    torch::Tensor ridx, torch::Tensor ridx_out, torch::Tensor gseg,
+    torch::Tensor gseg_out, torch::Tensor meta, torch::Tensor scalars,
+    torch::Tensor left_before, torch::Tensor node_left_total,
+    torch::Tensor flags, torch::Tensor cb) {
+  partition_scatter_planned(ridx, ridx_out, gseg, gseg_out, meta, scalars,
+                            left_before, node_left_total, flags,
+                            cb.item<int64_t>());
 }
 
 // Two-phase partition: `begin` launches count+prefix and returns
@@ -3172,7 +3624,7 @@ std::vector<torch::Tensor> depth_step(
     torch::Tensor counts_cpu, torch::Tensor fb, double scale_g,
     double scale_h, double lam, double alpha, double gamma, double mcw,
     torch::Tensor mono, torch::Tensor bounds, torch::Tensor allowed,
-    int64_t n_bins, int64_t chunk_bound) {
+    int64_t n_bins, int64_t chunk_bound, bool fused_glue) {
   auto dev = bins.device();
   auto stream = c10::hip::getCurrentHIPStream();
   const int F = (int)bins.size(1);
@@ -3193,29 +3645,46 @@ std::vector<torch::Tensor> depth_step(
   hist.narrow(0, 0, K_built).zero_();
   build_histogram(bins, gseg, ridx, starts_cpu, counts_cpu, n_bins, 0, F,
                   hist, /*pregathered=*/true);
-  // sibling = parent - built
+  // sibling = parent - built: inside the scan kernel (fused_glue) or as
+  // torch index_select + sub
+  OptTensor d_prev, d_pslots, d_spos;
   if (nd > 0) {
     auto pslots = dmeta.narrow(0, 4 * KK, nd);
     auto spos = dmeta.narrow(0, 4 * KK + nd, nd);
-    auto derived = hist.narrow(0, K_built, nd);
-    torch::sub_out(derived, prev_hist.index_select(0, pslots),
-                   hist.index_select(0, spos));
+    if (fused_glue) {
+      d_prev = prev_hist;
+      d_pslots = pslots;
+      d_spos = spos;
+    } else {
+      auto derived = hist.narrow(0, K_built, nd);
+      torch::sub_out(derived, prev_hist.index_select(0, pslots),
+                     hist.index_select(0, spos));
+    }
   }
-  // scan
-  auto fs = find_splits(hist, pg, ph, fb, scale_g, scale_h, lam, alpha,
-                        gamma, mcw, mono, bounds, allowed,
-                        /*pull=*/false);
-  auto packed = fs[0];
-  // device-planned partition (writes into ridx_dest, no clones)
-  auto st = partition_rows_from_packed(bins, ridx, d_starts, d_counts,
-                                       packed, gseg, bins_t, chunk_bound,
-                                       ridx_dest);
+  // scan + device-planned partition (writes into ridx_dest, no clones)
+  std::vector<torch::Tensor> st;
+  if (fused_glue) {
+    auto kf = find_splits_kf(hist, pg, ph, fb, scale_g, scale_h, lam, alpha,
+                             gamma, mcw, mono, bounds, allowed, d_prev,
+                             d_pslots, d_spos);
+    st = partition_rows_from_kf(bins, ridx, d_starts, d_counts, kf[0], kf[1],
+                                kf[2], kf[3], kf[4], gseg, bins_t,
+                                chunk_bound, ridx_dest);
+  } else {
+    auto fs = find_splits(hist, pg, ph, fb, scale_g, scale_h, lam, alpha,
+                          gamma, mcw, mono, bounds, allowed,
+                          /*pull=*/false, c10::nullopt, c10::nullopt,
+                          c10::nullopt);
+    st = partition_rows_from_packed(bins, ridx, d_starts, d_counts, fs[0],
+                                    gseg, bins_t, chunk_bound, ridx_dest,
+                                    /*fused_glue=*/false);
+  }
   // record the pull event BETWEEN the pull copies and the scatter
   if (!g_pull_event)
     (void)hipEventCreateWithFlags(&g_pull_event, hipEventDisableTiming);
   (void)hipEventRecord(g_pull_event, stream.stream());
-  partition_scatter_from_packed(ridx, st[0], gseg, st[1], st[3], st[4],
-                                st[5], st[6], st[7], st[8]);
+  partition_scatter_planned(ridx, st[0], gseg, st[1], st[3], st[4], st[5],
+                            st[6], st[7], chunk_bound);
   return {st[0], st[1], st[2]};
 }
 
@@ -3230,18 +3699,52 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("eval_auc_hist", &eval_auc_hist, "fused AUC score histograms");
   m.def("bin_matrix", &bin_matrix, "bin feature matrix");
   m.def("build_histogram", &build_histogram, "build gradient histograms");
-  m.def("find_splits", &find_splits, "best-split scan");
+  m.def("find_splits", &find_splits, "best-split scan", py::arg("hist"),
+        py::arg("parent_g"), py::arg("parent_h"), py::arg("feat_bins"),
+        py::arg("scale_g"), py::arg("scale_h"), py::arg("lam"),
+        py::arg("alpha"), py::arg("gamma"), py::arg("mcw"), py::arg("mono"),
+        py::arg("bounds"), py::arg("allowed"), py::arg("pull"),
+        py::arg("prev_hist") = py::none(), py::arg("pslots") = py::none(),
+        py::arg("spos") = py::none());
+  m.def("find_splits_kf", &find_splits_kf,
+        "(node, feature) split scan without the per-node reduce",
+        py::arg("hist"), py::arg("parent_g"), py::arg("parent_h"),
+        py::arg("feat_bins"), py::arg("scale_g"), py::arg("scale_h"),
+        py::arg("lam"), py::arg("alpha"), py::arg("gamma"), py::arg("mcw"),
+        py::arg("mono"), py::arg("bounds"), py::arg("allowed"),
+        py::arg("prev_hist") = py::none(), py::arg("pslots") = py::none(),
+        py::arg("spos") = py::none());
+  m.def("reduce_plan_fused", &reduce_plan_fused,
+        "per-node best split + partition plan, one kernel at K <= 1024");
+  m.def("reduce_plan_legacy", &reduce_plan_legacy,
+        "per-node best split + partition plan, the two separate kernels");
   m.def("partition_rows", &partition_rows, "stable row partition");
   m.def("partition_rows_begin", &partition_rows_begin,
         "count+prefix phase (returns before the host sync)");
   m.def("partition_rows_finish", &partition_rows_finish,
         "left-totals pull + scatter phase");
   m.def("partition_rows_from_packed", &partition_rows_from_packed,
-        "device-planned partition consuming find_splits packed output");
+        "device-planned partition consuming find_splits packed output",
+        py::arg("bins"), py::arg("ridx"), py::arg("starts_ord"),
+        py::arg("counts_ord"), py::arg("packed"), py::arg("gseg"),
+        py::arg("bins_t"), py::arg("chunk_bound"), py::arg("ridx_dest"),
+        py::arg("fused_glue") = false);
+  m.def("partition_rows_from_kf", &partition_rows_from_kf,
+        "device-planned partition consuming find_splits_kf output");
+  m.def("partition_scatter_planned", &partition_scatter_planned,
+        "scatter phase of the device-planned partition, integer chunk bound");
   m.def("partition_scatter_from_packed", &partition_scatter_from_packed,
         "scatter phase of the device-planned partition");
   m.def("depth_step", &depth_step,
-        "one fused single-sync depth (single-GPU fast path)");
+        "one fused single-sync depth (single-GPU fast path)",
+        py::arg("bins"), py::arg("bins_t"), py::arg("gseg"), py::arg("ridx"),
+        py::arg("ridx_dest"), py::arg("prev_hist"), py::arg("hist"),
+        py::arg("depth_meta_cpu"), py::arg("KK"), py::arg("nd"),
+        py::arg("K_built"), py::arg("starts_cpu"), py::arg("counts_cpu"),
+        py::arg("fb"), py::arg("scale_g"), py::arg("scale_h"), py::arg("lam"),
+        py::arg("alpha"), py::arg("gamma"), py::arg("mcw"), py::arg("mono"),
+        py::arg("bounds"), py::arg("allowed"), py::arg("n_bins"),
+        py::arg("chunk_bound"), py::arg("fused_glue") = false);
   m.def("wait_pull_event", &wait_pull_event,
         "host wait for the depth_step pull event");
   m.def("predict_trees", &predict_trees, "tree-walk prediction");

@@ -983,6 +983,16 @@ class BoostingEngine:
             and (_rf == "2"
                  or self.dtrain.bins.stride(0) <= _ROW_FINISH_MAX_STRIDE)
         )
+        # fused per-depth glue (GPU, per tree like RXGB_ONE_SYNC): the
+        # sibling histograms are derived inside the split scan, the
+        # per-node reduce and the partition plan are one kernel, the
+        # partition needs no zero fills and one pull brings
+        # {splits | left counts} to the host. RXGB_FUSED_GLUE=0 restores
+        # the separate torch/kernel composition exactly.
+        fused_glue = (
+            self.device.type == "cuda"
+            and _os2.environ.get("RXGB_FUSED_GLUE", "1") != "0"
+        )
         ridx_bufs = None
         cur_buf = 0
         if use_fused_loop:
@@ -1061,12 +1071,15 @@ class BoostingEngine:
                 (nF, F, self.n_bins, 2), dtype=torch.int64, device=self.device
             )
 
-            # depth_step (one C++ call per depth) measured slightly
-            # SLOWER than the python-orchestrated fused loop in a
-            # same-box interleaved A/B (3.23-3.36 vs 3.20-3.21
-            # ms/round): per-depth python/torch dispatch is not on the
-            # critical path - the residual wall gap is event-wait and
-            # launch bubbles. Kept opt-in (RXGB_DEPTH_STEP=1).
+            # depth_step (one C++ call per depth) measures SLOWER than
+            # the python-orchestrated fused loop in a same-box
+            # interleaved A/B: 2.75-2.96 vs 2.53-2.62 ms/round with the
+            # fused glue in both arms (3.23-3.36 vs 3.20-3.21 before the
+            # row-order finish and the fused glue). Per-depth
+            # python/torch dispatch is not on the critical path, and
+            # depth_step still partitions the last level, which the
+            # row-order finish skips in the python loop. Kept opt-in
+            # (RXGB_DEPTH_STEP=1).
             use_depth_step = (
                 use_fused_loop and not self.coll.is_distributed
                 and _os2.environ.get("RXGB_DEPTH_STEP") == "1"
@@ -1133,7 +1146,7 @@ class BoostingEngine:
                     scale_h, self.p.reg_lambda,
                     self.p.reg_alpha, self.p.gamma,
                     self.p.min_child_weight, mono_t, bounds_t,
-                    allowed_t, self.n_bins, chunk_bound,
+                    allowed_t, self.n_bins, chunk_bound, fused_glue,
                 )
                 depth_in_buf = cur_buf
                 cur_buf = 1 - cur_buf
@@ -1215,7 +1228,14 @@ class BoostingEngine:
                     ph = torch.from_numpy(sumh_ord)
                     pslots = torch.from_numpy(derive_pslot)
                     spos = torch.from_numpy(derive_sib_pos)
-                if nd:
+                derive_kw = {}
+                if nd and fused_glue:
+                    # sibling = parent - built inside the scan kernel,
+                    # which stores the derived rows for the next depth
+                    derive_kw = dict(
+                        prev_hist=prev_all_hist, pslots=pslots, spos=spos
+                    )
+                elif nd:
                     # sibling = parent - built, batched over all pairs
                     torch.sub(
                         prev_all_hist.index_select(0, pslots),
@@ -1250,19 +1270,28 @@ class BoostingEngine:
                         self.p.reg_lambda, self.p.reg_alpha, self.p.gamma,
                         self.p.min_child_weight, monotone=self.mono,
                         bounds=mono_bounds, allowed=allowed_m, pull=False,
+                        reduce=not fused_glue, **derive_kw,
                     )
                     _tick("scan")
                     # grid BOUND: every split node adds at most one
                     # partial chunk (PART_CHUNK = 2048 rows/workgroup)
                     frontier_rows = int(count_ord.sum())
                     chunk_bound = (frontier_rows + 2047) // 2048 + KK
+                    # fused glue: packed_dev is the (node, feature) scan
+                    # tuple, reduced inside the partition's plan kernel
+                    part_fn = (
+                        ops.partition_rows_from_kf if fused_glue
+                        else ops.partition_rows_from_packed
+                    )
+                    part_kw = {} if fused_glue else {"fused_glue": False}
                     ridx, gseg, pull, pull_ev = (
-                        ops.partition_rows_from_packed(
+                        part_fn(
                             self.dtrain.bins, ridx, d_starts, d_counts,
                             packed_dev, gseg,
                             getattr(self.dtrain, "bins_t", None),
                             chunk_bound,
                             ridx_dest=ridx_bufs[1 - cur_buf],
+                            **part_kw,
                         )
                     )
                     depth_in_buf = cur_buf
@@ -1296,6 +1325,7 @@ class BoostingEngine:
                         monotone=self.mono,
                         bounds=mono_bounds,
                         allowed=allowed_m,
+                        **derive_kw,
                     )
                     _tick("scan")
                     gain = best["gain"]

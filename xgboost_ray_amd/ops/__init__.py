@@ -119,6 +119,10 @@ def find_splits(
     bounds=None,
     allowed=None,
     pull=True,
+    prev_hist=None,
+    pslots=None,
+    spos=None,
+    reduce=True,
 ):
     """Best-split scan over histograms.
 
@@ -128,10 +132,21 @@ def find_splits(
       gain f32, feature i32, bin i32, default_left u8,
       left_g/left_h int64 (quantized left-child sums incl. missing if
       default_left).
+
+    GPU only: ``prev_hist``/``pslots``/``spos`` derive the trailing
+    sibling rows of ``hist`` inside the scan kernel, ``reduce=False``
+    returns the (node, feature) scan arrays for ``partition_rows_from_kf``
+    (see ops.gpu.find_splits).
     """
     kw = {}
     if hist.is_cuda:
         kw["pull"] = pull  # CPU impl always returns host arrays
+        kw["prev_hist"] = prev_hist
+        kw["pslots"] = pslots
+        kw["spos"] = spos
+        kw["reduce"] = reduce
+    elif prev_hist is not None or not reduce:
+        raise ValueError("in-kernel sibling derivation is GPU only")
     return _impl(hist).find_splits(
         hist,
         parent_g,
@@ -167,13 +182,26 @@ def partition_finish(ctx):
 
 
 def partition_rows_from_packed(bins, ridx, starts_ord, counts_ord, packed,
-                               gseg, bins_t, chunk_bound, ridx_dest=None):
+                               gseg, bins_t, chunk_bound, ridx_dest=None,
+                               fused_glue=None):
     """Single-sync fused partition (GPU only): see ops.gpu."""
     from xgboost_ray_amd.ops import gpu
 
     return gpu.partition_rows_from_packed(
         bins, ridx, starts_ord, counts_ord, packed, gseg, bins_t,
-        chunk_bound, ridx_dest,
+        chunk_bound, ridx_dest, fused_glue,
+    )
+
+
+def partition_rows_from_kf(bins, ridx, starts_ord, counts_ord, kf, gseg,
+                           bins_t, chunk_bound, ridx_dest=None):
+    """Single-sync fused partition fed by ``find_splits(reduce=False)``
+    (GPU only): see ops.gpu."""
+    from xgboost_ray_amd.ops import gpu
+
+    return gpu.partition_rows_from_kf(
+        bins, ridx, starts_ord, counts_ord, kf, gseg, bins_t, chunk_bound,
+        ridx_dest,
     )
 
 

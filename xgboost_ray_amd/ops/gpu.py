@@ -105,7 +105,18 @@ def find_splits(
     bounds=None,
     allowed=None,
     pull=True,
+    prev_hist=None,
+    pslots=None,
+    spos=None,
+    reduce=True,
 ):
+    """``prev_hist``/``pslots``/``spos``: derive the last ``len(pslots)``
+    rows of ``hist`` inside the scan kernel as
+    ``prev_hist[pslots] - hist[spos]`` (stored into ``hist``) instead of
+    materializing them beforehand. ``reduce=False`` returns the (node,
+    feature) scan arrays ``(gain, bin, dl, lg, lh)`` on device for
+    ``partition_rows_from_kf``, which folds the per-node reduce into the
+    partition plan."""
     import numpy as np
 
     dev = hist.device
@@ -116,7 +127,10 @@ def find_splits(
         allowed = torch.zeros(0, dtype=torch.uint8, device=dev)
     else:
         allowed = allowed.to(dev).to(torch.uint8).contiguous()
-    (packed,) = _load().find_splits(
+    derive = (None, None, None)
+    if prev_hist is not None and pslots is not None and len(pslots):
+        derive = (prev_hist, pslots.to(dev), spos.to(dev))
+    args = (
         hist,
         parent_g.to(dev),
         parent_h.to(dev),
@@ -130,8 +144,10 @@ def find_splits(
         monotone.to(dev).to(torch.int8),
         bounds.to(dev).to(torch.float64),
         allowed,
-        pull,
     )
+    if not reduce:
+        return tuple(_load().find_splits_kf(*args, *derive))
+    (packed,) = _load().find_splits(*args, pull, *derive)
     if not pull:
         return packed  # device [K,6] for the fused single-sync partition
     arr = packed.cpu().numpy()  # ONE D2H for the whole depth's splits
@@ -247,12 +263,14 @@ def grad_fused(margin, label, weight, scale_pos_weight, mode):
 PART_CHUNK = 2048
 
 
-def partition_rows_from_packed(bins, ridx, starts_ord, counts_ord, packed,
-                               gseg, bins_t, chunk_bound, ridx_dest=None):
-    """Single-sync partition: consumes find_splits' device packed output
-    (plan + count + prefix + scatter all device-planned); returns
-    (ridx_out, gseg_out, pull) where `pull` is a pinned i64 [7K] buffer
-    [packed rows | left_counts] valid after a stream sync."""
+def fused_glue_enabled():
+    """RXGB_FUSED_GLUE (default on; "0" restores the separate derive /
+    reduce / plan / fill / pull composition). Read per call, so callers
+    decide per tree and tests can toggle it within one process."""
+    return os.environ.get("RXGB_FUSED_GLUE", "1") != "0"
+
+
+def _partition_args(bins, gseg, bins_t, ridx_dest):
     dev = bins.device
     if bins_t is None:
         bins_t = torch.zeros(0, dtype=torch.uint8, device=dev)
@@ -260,19 +278,59 @@ def partition_rows_from_packed(bins, ridx, starts_ord, counts_ord, packed,
         gseg = torch.zeros((0, 2), dtype=torch.int32, device=dev)
     rd = ridx_dest if ridx_dest is not None else torch.zeros(
         0, dtype=torch.int32, device=bins.device)
-    out = _load().partition_rows_from_packed(
-        bins, ridx, starts_ord, counts_ord, packed, gseg, bins_t,
-        int(chunk_bound), rd,
-    )
+    return gseg, bins_t, rd
+
+
+def _scatter_after_pull(ridx, gseg, out, chunk_bound):
     # out: [ridx_out, gseg_out, pull, meta, scalars, left_before,
     #       node_left_total, flags, chunk_bound]
     ev = torch.cuda.Event()
     ev.record()  # after plan+count+prefix+pull, BEFORE the scatter
-    _load().partition_scatter_from_packed(
+    _load().partition_scatter_planned(
         ridx, out[0], gseg, out[1], out[3], out[4], out[5], out[6],
-        out[7], out[8],
+        out[7], int(chunk_bound),
     )
     return out[0], out[1], out[2], ev
+
+
+def partition_rows_from_packed(bins, ridx, starts_ord, counts_ord, packed,
+                               gseg, bins_t, chunk_bound, ridx_dest=None,
+                               fused_glue=None):
+    """Single-sync partition: consumes find_splits' device packed output
+    (plan + count + prefix + scatter all device-planned); returns
+    (ridx_out, gseg_out, pull, ev) where `pull` is a pinned i64 [7K]
+    buffer [packed rows | left_counts] valid once `ev` has completed.
+    ``fused_glue`` (default: RXGB_FUSED_GLUE) drops the zero fills and
+    takes the shuffle-scan prefix kernel."""
+    if fused_glue is None:
+        fused_glue = fused_glue_enabled()
+    gseg, bins_t, rd = _partition_args(bins, gseg, bins_t, ridx_dest)
+    out = _load().partition_rows_from_packed(
+        bins, ridx, starts_ord, counts_ord, packed, gseg, bins_t,
+        int(chunk_bound), rd, bool(fused_glue),
+    )
+    return _scatter_after_pull(ridx, gseg, out, chunk_bound)
+
+
+def partition_rows_from_kf(bins, ridx, starts_ord, counts_ord, kf, gseg,
+                           bins_t, chunk_bound, ridx_dest=None):
+    """partition_rows_from_packed fed by ``find_splits(reduce=False)``:
+    the per-node reduce and the partition plan run as one kernel, `packed`
+    and the left totals share one device buffer and reach the host in one
+    copy. Same return value."""
+    gseg, bins_t, rd = _partition_args(bins, gseg, bins_t, ridx_dest)
+    out = _load().partition_rows_from_kf(
+        bins, ridx, starts_ord, counts_ord, *kf, gseg, bins_t,
+        int(chunk_bound), rd,
+    )
+    return _scatter_after_pull(ridx, gseg, out, chunk_bound)
+
+
+def reduce_plan(kf, starts_ord, counts_ord, fused=True):
+    """Per-node best split + partition plan from the (node, feature) scan
+    arrays; returns (packed [K,6], meta, scalars [2]) on device."""
+    fn = _load().reduce_plan_fused if fused else _load().reduce_plan_legacy
+    return tuple(fn(*kf, starts_ord, counts_ord))
 
 
 def partition_begin(bins, ridx, starts, counts, split_feat, split_bin,

@@ -3365,12 +3365,19 @@ torch::Tensor lambdarank_grad(torch::Tensor margin, torch::Tensor label,
 // plus the two abs().max() reduction passes for the hot objectives -
 // the margin/label are read once and the fp32 gpair written once.
 // The f32 op ORDER replicates torch's eager kernels exactly
-// (p = 1/(1+expf(-x)); h = fmaxf(p*(1-p), eps); per-factor multiplies in
+// (p = 1/(1+expf(-x)); h = max(p*(1-p), eps); per-factor multiplies in
 // the same sequence), so models stay bitwise-identical to the CPU
-// oracle. The max reduction is order-free (fmax is associative).
+// oracle. The max reduction is order-free (max is associative) and, like
+// torch's abs().max() and clamp(), keeps NaN: fmaxf would drop it, and a
+// diverged margin would quantize as if it were finite.
 // MODE 0: reg:squarederror (g = m - y, h = 1)
 // MODE 1: binary:logistic  (g = p - y, h = max(p(1-p), 1e-16))
 // ---------------------------------------------------------------------------
+// max(a, b) that returns NaN when either side is NaN
+__device__ __forceinline__ float max_keep_nan(float a, float b) {
+  return (b > a || b != b) ? b : a;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void grad_fused_kernel(
     const float* __restrict__ margin, const float* __restrict__ label,
@@ -3388,7 +3395,8 @@ __global__ __launch_bounds__(256) void grad_fused_kernel(
     if constexpr (MODE == 1) {
       const float p = 1.0f / (1.0f + expf(-x));
       g = p - y;
-      h = fmaxf(p * (1.0f - p), 1e-16f);
+      const float pq = p * (1.0f - p);
+      h = pq < 1e-16f ? 1e-16f : pq;  // NaN stays NaN, as torch.clamp
       if (spw != 1.0f) {
         const float w = 1.0f + (spw - 1.0f) * y;
         g *= w;
@@ -3404,8 +3412,8 @@ __global__ __launch_bounds__(256) void grad_fused_kernel(
       h *= w;
     }
     gpair[i] = {g, h};
-    gmax = fmaxf(gmax, fabsf(g));
-    hmax = fmaxf(hmax, fabsf(h));
+    gmax = max_keep_nan(gmax, fabsf(g));
+    hmax = max_keep_nan(hmax, fabsf(h));
   }
   // wave reduce -> LDS -> one [2]-float store per BLOCK. A global
   // atomicMax per wave serialized 43k atomics on TWO L2 addresses and
@@ -3414,8 +3422,8 @@ __global__ __launch_bounds__(256) void grad_fused_kernel(
   __shared__ float red[2 * 256 / WAVE];
   #pragma unroll
   for (int off = WAVE / 2; off > 0; off >>= 1) {
-    gmax = fmaxf(gmax, __shfl_down(gmax, off, WAVE));
-    hmax = fmaxf(hmax, __shfl_down(hmax, off, WAVE));
+    gmax = max_keep_nan(gmax, __shfl_down(gmax, off, WAVE));
+    hmax = max_keep_nan(hmax, __shfl_down(hmax, off, WAVE));
   }
   const int wid = threadIdx.x / WAVE;
   if ((threadIdx.x & (WAVE - 1)) == 0) {
@@ -3427,8 +3435,8 @@ __global__ __launch_bounds__(256) void grad_fused_kernel(
     const int nw = blockDim.x / WAVE;
     float g = red[0], h = red[1];
     for (int w = 1; w < nw; ++w) {
-      g = fmaxf(g, red[2 * w]);
-      h = fmaxf(h, red[2 * w + 1]);
+      g = max_keep_nan(g, red[2 * w]);
+      h = max_keep_nan(h, red[2 * w + 1]);
     }
     block_max[2 * (size_t)blockIdx.x] = g;
     block_max[2 * (size_t)blockIdx.x + 1] = h;
@@ -3471,7 +3479,8 @@ std::vector<torch::Tensor> grad_fused(torch::Tensor margin,
                        (float2*)gpair.data_ptr<float>(),
                        block_max.data_ptr<float>(), n);
   }
-  // fmax is order-free, so this equals abs().max() bitwise
+  // max is order-free and torch's max keeps NaN, so this equals
+  // abs().max() bitwise
   auto absmax = std::get<0>(block_max.max(0));
   return {gpair, absmax};
 }
@@ -3495,7 +3504,9 @@ __global__ __launch_bounds__(256) void eval_logloss_kernel(
        i += stride) {
     // same math as metrics.LogLoss: sigmoid in f64, clamped p
     double p = 1.0 / (1.0 + exp(-(double)margin[i]));
-    p = fmin(fmax(p, 1e-16), 1.0 - 1e-16);
+    // comparisons, not fmin/fmax: a NaN margin stays NaN (torch.clamp
+    // does the same), so a diverged run cannot report a finite loss
+    p = p < 1e-16 ? 1e-16 : (p > 1.0 - 1e-16 ? 1.0 - 1e-16 : p);
     const double y = (double)label[i];
     const double w = weight ? (double)weight[i] : 1.0;
     ll += w * -(y * log(p) + (1.0 - y) * log(1.0 - p));
@@ -3577,6 +3588,14 @@ torch::Tensor eval_auc_hist(torch::Tensor margin, torch::Tensor label,
                             int64_t n_bins) {
   const int64_t n = margin.numel();
   auto dev = margin.device();
+  // two u32 planes of n_bins in dynamic LDS; a larger request fails the
+  // launch and would leave the histogram all zero
+  constexpr int64_t kAucLdsBytes = 160 * 1024;
+  TORCH_CHECK(n_bins >= 1 &&
+                  2 * n_bins * (int64_t)sizeof(unsigned int) <= kAucLdsBytes,
+              "eval_auc_hist: n_bins must be in [1, ",
+              kAucLdsBytes / (2 * (int64_t)sizeof(unsigned int)), "], got ",
+              n_bins);
   auto hist = torch::zeros(
       {2 * n_bins},
       torch::TensorOptions().dtype(torch::kInt64).device(dev));
@@ -3586,9 +3605,9 @@ torch::Tensor eval_auc_hist(torch::Tensor margin, torch::Tensor label,
   static bool lds_attr_set = false;
   if (!lds_attr_set) {
     // dynamic LDS above 64 KiB needs the opt-in attribute (160 KiB/CU)
-    (void)hipFuncSetAttribute(
+    CHECK_HIP(hipFuncSetAttribute(
         reinterpret_cast<const void*>(&eval_auc_hist_kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAucLdsBytes));
     lds_attr_set = true;
   }
   const int64_t blocks = std::min<int64_t>(ceil_div(n, 256 * 64), 256);
@@ -3597,6 +3616,7 @@ torch::Tensor eval_auc_hist(torch::Tensor margin, torch::Tensor label,
                      margin.data_ptr<float>(), label.data_ptr<float>(),
                      reinterpret_cast<long long*>(hist.data_ptr<int64_t>()),
                      (int)n_bins, n);
+  CHECK_HIP(hipGetLastError());
   return hist;  // [neg | pos] planes
 }
 

@@ -300,24 +300,31 @@ class LambdaRankBase(Objective):
             pos = diff_y > 0  # i more relevant than j
             if not bool(pos.any()):
                 continue
-            sij = m.unsqueeze(1) - m.unsqueeze(0)
+            # every pair term in float64, from the score difference formed
+            # in the margin's own precision - the HIP kernel's
+            # (double)(mi - mj). In float32, 1 - rho cancels for a badly
+            # misordered pair and disc_i - disc_j cancels for neighbouring
+            # ranks; only the per-row accumulation below stays float32.
+            sij = (m.unsqueeze(1) - m.unsqueeze(0)).double()
             rho = torch.sigmoid(-sij)  # d/ds_i of log-loss for pair (i,j)
             lam = rho
             hess = torch.clamp(rho * (1.0 - rho), min=_EPS)
             if getattr(self, "map_weighting", False):
                 # |delta AP| for swapping i, j at the current ranking
                 # (binary relevance; closed form via 1/k prefix sums)
-                rel = (y > 0).to(m.dtype)
+                rel = (y > 0).double()
                 R = rel.sum()
                 if float(R) <= 0:
                     continue
-                order = torch.argsort(m, descending=True)
+                # stable: tied margins (all of round 0) rank in row order,
+                # as on the HIP path
+                order = torch.argsort(m, descending=True, stable=True)
                 rank = torch.empty_like(order)
                 rank[order] = torch.arange(e - s, device=device)
                 rel_sorted = rel[order]
                 prefix = torch.cumsum(rel_sorted, 0)  # rel count in top k+1
                 invk = 1.0 / torch.arange(
-                    1, e - s + 1, device=device, dtype=m.dtype
+                    1, e - s + 1, device=device, dtype=torch.float64
                 )
                 S = torch.cumsum(rel_sorted * invk, 0)  # sum 1/k over rel
                 # per-doc terms at its own rank (0-based rank r -> k=r+1)
@@ -339,15 +346,17 @@ class LambdaRankBase(Objective):
                 lam = lam * delta
                 hess = hess * delta
             elif self.ndcg_weighting:
-                # |delta NDCG| for swapping i, j at current ranking
-                order = torch.argsort(m, descending=True)
+                # |delta NDCG| for swapping i, j at current ranking (stable
+                # order: ties rank in row order, as on the HIP path)
+                order = torch.argsort(m, descending=True, stable=True)
                 rank = torch.empty_like(order)
                 rank[order] = torch.arange(e - s, device=device)
-                gain = torch.pow(2.0, y) - 1.0
-                disc = 1.0 / torch.log2(rank.to(m.dtype) + 2.0)
+                gain = torch.pow(2.0, y.double()) - 1.0
+                disc = 1.0 / torch.log2(rank.double() + 2.0)
                 ideal_gain, _ = torch.sort(gain, descending=True)
                 ideal_disc = 1.0 / torch.log2(
-                    torch.arange(e - s, device=device, dtype=m.dtype) + 2.0
+                    torch.arange(e - s, device=device, dtype=torch.float64)
+                    + 2.0
                 )
                 idcg = (ideal_gain * ideal_disc).sum()
                 if idcg <= 0:
@@ -357,8 +366,8 @@ class LambdaRankBase(Objective):
                 delta = torch.abs(dg * dd) / idcg
                 lam = lam * delta
                 hess = hess * delta
-            lam = torch.where(pos, lam, torch.zeros_like(lam))
-            hess = torch.where(pos, hess, torch.zeros_like(hess))
+            lam = torch.where(pos, lam, torch.zeros_like(lam)).to(g.dtype)
+            hess = torch.where(pos, hess, torch.zeros_like(hess)).to(g.dtype)
             # pair (i, j): i should rank above j -> push m_i up, m_j down
             g[s:e] += -lam.sum(dim=1) + lam.sum(dim=0)
             h[s:e] += hess.sum(dim=1) + hess.sum(dim=0)

@@ -553,12 +553,22 @@ __global__ __launch_bounds__(THREADS) void build_histogram_xcd_kernel(
     const int64_t* __restrict__ chunk_off,   // [K+1] cumulative chunks
     long long* __restrict__ hist,            // [K, F, n_bins, 2]
     int K, int F, int n_bins, int n_fb, int64_t row_stride, int f_base,
-    int rows_per_wg, int total_chunks, int direct_rows) {
+    int rows_per_wg, int total_chunks, int direct_rows,
+    // device-limit form (nullptr: off): {K, KK, total_chunks} written by
+    // plan_next_depth_kernel. K and total_chunks are then BOUNDS, excess
+    // workgroups exit, and node_start is the depth's histogram meta
+    // [starts K | counts K | chunk_off K+1] at true-K offsets.
+    const int64_t* __restrict__ limits) {
   const int flat = blockIdx.x;
   const int octet = flat / (8 * n_fb);
   const int rem = flat % (8 * n_fb);
   const int fb = rem / 8;
   const int wg = octet * 8 + (rem % 8);  // row-chunk id
+  if (limits != nullptr) {
+    K = (int)limits[0];
+    total_chunks = (int)limits[2];
+    chunk_off = node_start + 2 * (int64_t)K;
+  }
   if (wg >= total_chunks) return;        // tail of the last chunk-octet
 
   int lo = 0, hi = K;
@@ -690,7 +700,20 @@ __global__ __launch_bounds__(256) void find_splits_kf_kernel(
     uint8_t* __restrict__ out_dl,      // [K, F]
     long long* __restrict__ out_lg,    // [K, F]
     long long* __restrict__ out_lh,    // [K, F]
-    int K, int F, int B) {
+    int K, int F, int B,
+    // device-limit form (nullptr: off): limits = {K_built, K, ...} and the
+    // depth's scan meta [sumg K | sumh K | starts K | counts K | pslot nd |
+    // spos nd] at true-K offsets, both written by plan_next_depth_kernel.
+    // The K argument is then a BOUND and excess waves exit.
+    const int64_t* __restrict__ limits, const int64_t* __restrict__ dmeta) {
+  if (limits != nullptr) {
+    K_built = (int)limits[0];
+    K = (int)limits[1];
+    parent_g = reinterpret_cast<const long long*>(dmeta);
+    parent_h = parent_g + K;
+    pslots = dmeta + 4 * (int64_t)K;
+    spos = pslots + (K - K_built);
+  }
   // ONE 64-lane wave per (node, feature). The per-bin left sums come
   // from an INT64 inclusive wave-scan (lane-local serial prefix over a
   // contiguous bin chunk + shfl_up scan of lane totals) - integer adds
@@ -1743,6 +1766,126 @@ static void cat_into_pinned(torch::Tensor out,
   torch::cat_out(out, parts);
 }
 
+// Histogram kernel flavour and its geometry for one launch: decided from
+// the matrix layout, the feature range, the built-node count and the
+// RXGB_HIST_* knobs. Shared by build_histogram and the whole-tree enqueue,
+// which must agree on rows_per_wg with the device-planned chunk offsets.
+struct HistConfig {
+  int64_t row_stride;
+  bool vec16;       // 16-byte-aligned row stride, n_bins <= 256
+  int fb;           // requested feature-block size (RXGB_HIST_FB)
+  bool multifb;     // register-cached block-sweep kernel
+  bool xcd;         // XCD-swizzled co-resident grid (default, >= 2 blocks)
+  int rows_per_wg;
+  int xcd_threads;
+  int direct_rows;
+  int mfb_r;
+};
+
+static HistConfig hist_config(const torch::Tensor& bins, int64_t n_bins,
+                              int64_t f_lo, int64_t f_hi, int K) {
+  HistConfig hc;
+  hc.row_stride = bins.stride(0);
+  hc.vec16 = (hc.row_stride % 16 == 0) && n_bins <= 256;
+  hc.fb = 16;
+  if (const char* e = getenv("RXGB_HIST_FB")) {
+    if (atoi(e) == 8) hc.fb = 8;
+  }
+  const int n_fb_pre =
+      hc.vec16 ? (int)ceil_div(f_hi - f_lo, (int64_t)hc.fb) : 1;
+  // multifb: one WG sweeps all feature blocks with register-cached
+  // gpairs/ridx (see kernel comment). Default on for multi-block ranges;
+  // RXGB_HIST_MULTIFB=0 disables, RXGB_HIST_MULTIFB_R in {8,16,32}.
+  // any multi-block range: with the SoA LDS layout + interleaved merge
+  // it wins at 2 blocks too (HIGGS 8.18 vs 8.31 ms/round) and by 11% at
+  // 13 blocks (100M x 200: 138.7 vs 155.6 ms/round at R=8).
+  bool multifb = hc.vec16 && hc.fb == 16 && n_fb_pre >= 2;
+  if (const char* e = getenv("RXGB_HIST_MULTIFB")) {
+    if (atoi(e) == 0) multifb = false;
+  }
+  // Default mode for multi-block ranges: XCD-swizzled co-resident grid
+  // (hist 102 -> 56 ms at 100M x 200; HIGGS 8.31 -> 7.25 ms/round).
+  // RXGB_HIST_MODE=multifb selects the register-cached block-sweep
+  // variant instead; =base the original (chunk, block) 2-D grid.
+  bool xcd_mode = multifb;
+  if (const char* e = getenv("RXGB_HIST_MODE")) {
+    if (strcmp(e, "multifb") == 0) xcd_mode = false;
+    else if (strcmp(e, "base") == 0) { xcd_mode = false; multifb = false; }
+  }
+  if (xcd_mode) multifb = false;
+  hc.multifb = multifb;
+  hc.xcd = xcd_mode;
+  // depth-aware chunk size: large frontiers (deep depths) have small
+  // per-node segments where 8192-row chunks load-balance better
+  // (measured d12 6.81 vs 6.84 ms/round); shallow depths keep 16384
+  // (fewer LDS tile merges per node; 16384 won the 100M sweep)
+  int xcd_rows = K >= 512 ? 8192 : 16384;
+  if (const char* e = getenv("RXGB_HIST_XCD_ROWS")) {
+    int v = atoi(e);
+    if (v >= 512 && v <= 65536) xcd_rows = v;
+  }
+  // R=8 (4096 rows/WG) measured best at 100M x 200: finer chunks load-
+  // balance deep depths better than R=16/32, and occupancy is LDS-bound.
+  // tiny-node threshold for the direct-to-global path. Default OFF:
+  // measured on HIGGS-11Mx28 depth 12, direct=512/1024/2048 gave
+  // 11.84/12.14/12.88 ms/round vs 11.65 with the LDS route - the
+  // skip-if-zero merge already makes empty tiles cheap, and the direct
+  // path's global-atomic latency is not hidden at 256-thread occupancy.
+  // Kept as an env knob for wider matrices / other shapes.
+  hc.direct_rows = 0;
+  if (const char* e = getenv("RXGB_HIST_DIRECT_ROWS")) {
+    int v = atoi(e);
+    if (v >= 0 && v <= 65536) hc.direct_rows = v;
+  }
+  hc.mfb_r = 8;
+  if (const char* e = getenv("RXGB_HIST_MULTIFB_R")) {
+    int v = atoi(e);
+    if (v == 4 || v == 8 || v == 16 || v == 32) hc.mfb_r = v;
+  }
+  hc.rows_per_wg = multifb ? hc.mfb_r * HIST_THREADS
+                   : xcd_mode ? xcd_rows
+                              : HIST_ROWS_PER_WG;
+  // 1024-thread WGs double waves/SIMD (2 WGs/CU within 160 KB LDS
+  // either way) and win on huge matrices (100M: hist 55.6 -> 53.9 ms)
+  // but lose ~3% on 11M-row shapes (deep-depth tail waste), so gate on
+  // matrix size; RXGB_HIST_XCD_THREADS=512/1024 overrides.
+  hc.xcd_threads = bins.size(0) > (int64_t)32 * 1024 * 1024 ? 1024 : 512;
+  if (const char* e = getenv("RXGB_HIST_XCD_THREADS")) {
+    int v = atoi(e);
+    if (v == 512 || v == 1024) hc.xcd_threads = v;
+  }
+  return hc;
+}
+
+// One launch of build_histogram_xcd_kernel over feature range [f_lo, F) of
+// a 16-byte-stride matrix. `limits` null: K/total_chunks exact, meta =
+// starts|counts at [0, 2K) and chunk_off separate; non-null: bounds, and
+// `meta` is the device-planned histogram meta (chunk_off ignored).
+static void launch_hist_xcd(const HistConfig& hc, const torch::Tensor& bins,
+                            const int2* gpair_seg, const int32_t* ridx,
+                            const int64_t* meta, const int64_t* chunk_off,
+                            long long* hist, int K, int n_bins, int f_lo,
+                            int f_hi, int64_t total_chunks,
+                            const int64_t* limits, hipStream_t stream) {
+  const int F = (int)bins.size(1);
+  const int n_fb = (int)ceil_div(f_hi - f_lo, 16);
+  const size_t lds = (size_t)16 * n_bins * 2 * sizeof(long long);
+  const int64_t grid = ceil_div(total_chunks, 8) * 8 * (int64_t)n_fb;
+  if (grid == 0) return;
+  auto launch_xcd = [&](auto tc) {
+    hipLaunchKernelGGL((build_histogram_xcd_kernel<decltype(tc)::value>),
+                       dim3((uint32_t)grid), dim3(decltype(tc)::value), lds,
+                       stream, bins.data_ptr<uint8_t>(), gpair_seg, ridx, meta,
+                       chunk_off, hist, K, F, n_bins, n_fb, hc.row_stride,
+                       f_lo, hc.rows_per_wg, (int)total_chunks,
+                       hc.direct_rows, limits);
+  };
+  if (hc.xcd_threads == 512)
+    launch_xcd(std::integral_constant<int, 512>{});
+  else
+    launch_xcd(std::integral_constant<int, 1024>{});
+}
+
 torch::Tensor build_histogram(torch::Tensor bins, torch::Tensor gpair_q,
                               torch::Tensor ridx, torch::Tensor starts,
                               torch::Tensor counts, int64_t n_bins,
@@ -1761,64 +1904,13 @@ torch::Tensor build_histogram(torch::Tensor bins, torch::Tensor gpair_q,
 
   // feature-block config decides the kernel flavor, which decides the
   // row-chunk size, so resolve it before computing chunk offsets.
-  const int64_t row_stride0 = bins.stride(0);
-  const bool vec16_pre = (row_stride0 % 16 == 0) && n_bins <= 256;
-  int fb_pre = 16;
-  if (const char* e = getenv("RXGB_HIST_FB")) {
-    if (atoi(e) == 8) fb_pre = 8;
-  }
-  const int n_fb_pre =
-      vec16_pre ? (int)ceil_div(f_hi - f_lo, (int64_t)fb_pre) : 1;
-  // multifb: one WG sweeps all feature blocks with register-cached
-  // gpairs/ridx (see kernel comment). Default on for multi-block ranges;
-  // RXGB_HIST_MULTIFB=0 disables, RXGB_HIST_MULTIFB_R in {8,16,32}.
-  // any multi-block range: with the SoA LDS layout + interleaved merge
-  // it wins at 2 blocks too (HIGGS 8.18 vs 8.31 ms/round) and by 11% at
-  // 13 blocks (100M x 200: 138.7 vs 155.6 ms/round at R=8).
-  bool multifb = vec16_pre && fb_pre == 16 && n_fb_pre >= 2;
-  if (const char* e = getenv("RXGB_HIST_MULTIFB")) {
-    if (atoi(e) == 0) multifb = false;
-  }
-  // Default mode for multi-block ranges: XCD-swizzled co-resident grid
-  // (hist 102 -> 56 ms at 100M x 200; HIGGS 8.31 -> 7.25 ms/round).
-  // RXGB_HIST_MODE=multifb selects the register-cached block-sweep
-  // variant instead; =base the original (chunk, block) 2-D grid.
-  bool xcd_mode = multifb;
-  if (const char* e = getenv("RXGB_HIST_MODE")) {
-    if (strcmp(e, "multifb") == 0) xcd_mode = false;
-    else if (strcmp(e, "base") == 0) { xcd_mode = false; multifb = false; }
-  }
-  if (xcd_mode) multifb = false;
-  // depth-aware chunk size: large frontiers (deep depths) have small
-  // per-node segments where 8192-row chunks load-balance better
-  // (measured d12 6.81 vs 6.84 ms/round); shallow depths keep 16384
-  // (fewer LDS tile merges per node; 16384 won the 100M sweep)
-  int xcd_rows = K >= 512 ? 8192 : 16384;
-  if (const char* e = getenv("RXGB_HIST_XCD_ROWS")) {
-    int v = atoi(e);
-    if (v >= 512 && v <= 65536) xcd_rows = v;
-  }
-  // R=8 (4096 rows/WG) measured best at 100M x 200: finer chunks load-
-  // balance deep depths better than R=16/32, and occupancy is LDS-bound.
-  // tiny-node threshold for the direct-to-global path. Default OFF:
-  // measured on HIGGS-11Mx28 depth 12, direct=512/1024/2048 gave
-  // 11.84/12.14/12.88 ms/round vs 11.65 with the LDS route - the
-  // skip-if-zero merge already makes empty tiles cheap, and the direct
-  // path's global-atomic latency is not hidden at 256-thread occupancy.
-  // Kept as an env knob for wider matrices / other shapes.
-  int direct_rows = 0;
-  if (const char* e = getenv("RXGB_HIST_DIRECT_ROWS")) {
-    int v = atoi(e);
-    if (v >= 0 && v <= 65536) direct_rows = v;
-  }
-  int mfb_r = 8;
-  if (const char* e = getenv("RXGB_HIST_MULTIFB_R")) {
-    int v = atoi(e);
-    if (v == 4 || v == 8 || v == 16 || v == 32) mfb_r = v;
-  }
-  const int rows_per_wg = multifb ? mfb_r * HIST_THREADS
-                          : xcd_mode ? xcd_rows
-                                     : HIST_ROWS_PER_WG;
+  const HistConfig hc = hist_config(bins, n_bins, f_lo, f_hi, K);
+  const int64_t row_stride0 = hc.row_stride;
+  const bool vec16_pre = hc.vec16;
+  const int fb_pre = hc.fb;
+  const bool multifb = hc.multifb, xcd_mode = hc.xcd;
+  const int direct_rows = hc.direct_rows, mfb_r = hc.mfb_r;
+  const int rows_per_wg = hc.rows_per_wg;
 
   int64_t total_chunks = 0;
   auto chunk_off_cpu =
@@ -1891,31 +1983,12 @@ torch::Tensor build_histogram(torch::Tensor bins, torch::Tensor gpair_q,
 
   // ridx pointer offset so seg indices align with gpair_seg
   if (xcd_mode) {
-    const int64_t grid = ceil_div(total_chunks, 8) * 8 * (int64_t)n_fb;
-    // 1024-thread WGs double waves/SIMD (2 WGs/CU within 160 KB LDS
-    // either way) and win on huge matrices (100M: hist 55.6 -> 53.9 ms)
-    // but lose ~3% on 11M-row shapes (deep-depth tail waste), so gate on
-    // matrix size; RXGB_HIST_XCD_THREADS=512/1024 overrides.
-    int xt = bins.size(0) > (int64_t)32 * 1024 * 1024 ? 1024 : 512;
-    if (const char* e = getenv("RXGB_HIST_XCD_THREADS")) {
-      int v = atoi(e);
-      if (v == 512 || v == 1024) xt = v;
-    }
-    auto launch_xcd = [&](auto tc) {
-      hipLaunchKernelGGL((build_histogram_xcd_kernel<decltype(tc)::value>),
-                         dim3((uint32_t)grid), dim3(decltype(tc)::value),
-                         lds, stream.stream(), bins.data_ptr<uint8_t>(),
-                         (const int2*)gpair_seg.data_ptr<int32_t>(),
-                         ridx.data_ptr<int32_t>() + min_start, sc_adj_p,
-                         chunk_off_p,
-                         reinterpret_cast<long long*>(hist.data_ptr<int64_t>()),
-                         K, F, (int)n_bins, n_fb, row_stride, (int)f_lo,
-                         rows_per_wg, (int)total_chunks, direct_rows);
-    };
-    if (xt == 512)
-      launch_xcd(std::integral_constant<int, 512>{});
-    else
-      launch_xcd(std::integral_constant<int, 1024>{});
+    launch_hist_xcd(hc, bins, (const int2*)gpair_seg.data_ptr<int32_t>(),
+                    ridx.data_ptr<int32_t>() + min_start, sc_adj_p,
+                    chunk_off_p,
+                    reinterpret_cast<long long*>(hist.data_ptr<int64_t>()), K,
+                    (int)n_bins, (int)f_lo, (int)f_hi, total_chunks, nullptr,
+                    stream.stream());
   } else if (multifb) {
     auto launch_mfb = [&](auto rc) {
       hipLaunchKernelGGL((build_histogram_multifb_kernel<decltype(rc)::value>),
@@ -1983,7 +2056,7 @@ std::vector<torch::Tensor> find_splits_kf(
     torch::Tensor feat_bins, double scale_g, double scale_h, double lam,
     double alpha, double gamma, double mcw, torch::Tensor mono,
     torch::Tensor bounds, torch::Tensor allowed, OptTensor prev_hist,
-    OptTensor pslots, OptTensor spos) {
+    OptTensor pslots, OptTensor spos, OptTensor limits, OptTensor dmeta) {
   const int K = (int)hist.size(0);
   const int F = (int)hist.size(1);
   const int B = (int)hist.size(2);
@@ -1991,8 +2064,34 @@ std::vector<torch::Tensor> find_splits_kf(
   const long long* prev_p = nullptr;
   const int64_t* pslots_p = nullptr;
   const int64_t* spos_p = nullptr;
+  const int64_t* limits_p = nullptr;
+  const int64_t* dmeta_p = nullptr;
   int K_built = K;
-  if (prev_hist.has_value() && pslots.has_value() && pslots->numel() > 0) {
+  if (limits.has_value()) {
+    // device-limit form: hist.size(0) bounds the frontier; node sums and
+    // the sibling map come from dmeta, parent_g/parent_h/pslots/spos are
+    // not read. prev_hist (when given) must hold every parent slot.
+    TORCH_CHECK(dmeta.has_value() && on_gpu(*limits) && on_gpu(*dmeta) &&
+                    limits->scalar_type() == torch::kInt64 &&
+                    dmeta->scalar_type() == torch::kInt64 &&
+                    limits->numel() >= 3 && dmeta->is_contiguous() &&
+                    dmeta->numel() >= 5 * (int64_t)K,
+                "find_splits: limits form needs device int64 limits[3] and "
+                "dmeta[>= 5K]");
+    limits_p = limits->data_ptr<int64_t>();
+    dmeta_p = dmeta->data_ptr<int64_t>();
+    if (prev_hist.has_value()) {
+      TORCH_CHECK(prev_hist->is_contiguous() && prev_hist->dim() == 4 &&
+                      prev_hist->size(1) == F && prev_hist->size(2) == B &&
+                      prev_hist->scalar_type() == torch::kInt64 &&
+                      prev_hist->data_ptr() != hist.data_ptr(),
+                  "find_splits: prev_hist must be contiguous int64 "
+                  "[*, F, B, 2] and must not alias hist");
+      prev_p =
+          reinterpret_cast<const long long*>(prev_hist->data_ptr<int64_t>());
+    }
+  } else if (prev_hist.has_value() && pslots.has_value() &&
+             pslots->numel() > 0) {
     TORCH_CHECK(spos.has_value() && spos->numel() == pslots->numel(),
                 "find_splits: pslots and spos must have equal length");
     const int64_t nd = pslots->numel();
@@ -2049,7 +2148,8 @@ std::vector<torch::Tensor> find_splits_kf(
                      kf_gain.data_ptr<double>(),
                      kf_bin.data_ptr<int32_t>(), kf_dl.data_ptr<uint8_t>(),
                      reinterpret_cast<long long*>(kf_lg.data_ptr<int64_t>()),
-                     reinterpret_cast<long long*>(kf_lh.data_ptr<int64_t>()), K, F, B);
+                     reinterpret_cast<long long*>(kf_lh.data_ptr<int64_t>()), K, F, B,
+                     limits_p, dmeta_p);
   return {kf_gain, kf_bin, kf_dl, kf_lg, kf_lh};
 }
 
@@ -2079,7 +2179,8 @@ std::vector<torch::Tensor> find_splits(torch::Tensor hist, torch::Tensor parent_
   const int F = (int)hist.size(1);
   auto kf = find_splits_kf(hist, parent_g, parent_h, feat_bins, scale_g,
                            scale_h, lam, alpha, gamma, mcw, mono, bounds,
-                           allowed, prev_hist, pslots, spos);
+                           allowed, prev_hist, pslots, spos, c10::nullopt,
+                           c10::nullopt);
   auto out_packed = torch::empty(
       {K, 6}, torch::TensorOptions().dtype(torch::kInt64).device(hist.device()));
   launch_reduce(kf, out_packed, K, F);
@@ -2202,7 +2303,16 @@ __global__ __launch_bounds__(RP_THREADS) void reduce_plan_kernel(
     long long* __restrict__ out_packed,      // [K, 6]
     int64_t* __restrict__ meta,     // [6K+1] compacted partition meta
     int64_t* __restrict__ scalars,  // [2]: n_split, total_chunks
-    int K, int F) {
+    int K, int F,
+    // device-limit form (nullptr: off): K = limits[1], starts/counts come
+    // from the depth's scan meta (layout: find_splits_kf_kernel). K == 0
+    // plans an empty partition.
+    const int64_t* __restrict__ limits, const int64_t* __restrict__ dmeta) {
+  if (limits != nullptr) {
+    K = (int)limits[1];
+    starts_ord = dmeta + 2 * (int64_t)K;
+    counts_ord = dmeta + 3 * (int64_t)K;
+  }
   __shared__ int s_gbits[RP_THREADS];
   __shared__ int s_feat[RP_THREADS];
   __shared__ int s_bin[RP_THREADS];
@@ -2318,6 +2428,148 @@ __global__ __launch_bounds__(RP_THREADS) void reduce_plan_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// plan_next_depth: depth d's split results -> depth d+1's launch metadata,
+// on device, so the next depth's histogram/scan/plan kernels need nothing
+// from the host. The integer transcription of the trainer's child
+// bookkeeping: per split node (scan slot k, compact position pos in
+// ascending-k order, the order reduce_plan_kernel compacted and the
+// partition's left totals are stored in)
+//   left  = (start,      lc,         lg,        lh)
+//   right = (start + lc, count - lc, sumg - lg, sumh - lh)
+// the child with the smaller quantized hessian sum is BUILT (tie: left),
+// the other is derived as parent - built. Built children take scan slots
+// [0, K'), their siblings [K', 2K') in the same order; K' = n_split.
+// Outputs, at true-K' offsets (KK' = 2K'):
+//   dmeta_next  [sumg KK' | sumh KK' | starts KK' | counts KK' |
+//                pslot K' | spos K']          (pslot = k, spos = pos)
+//   hmeta_next  [starts K' | counts K' | chunk_off K'+1]   built nodes
+//   limits_next {K', KK', total histogram chunks}
+// Single workgroup, thread k owns scan slot k (KK <= 1024); two wave-
+// shuffle scans with a 16-entry carry, like reduce_plan_kernel. Integer
+// math only. K' = 0 writes zero limits.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(RP_THREADS) void plan_next_depth_kernel(
+    const long long* __restrict__ packed,         // depth d [KK, 6]
+    const int64_t* __restrict__ dmeta,            // depth d scan meta
+    const int64_t* __restrict__ limits,           // depth d {K, KK, chunks}
+    const int64_t* __restrict__ node_left_total,  // [n_split] compact order
+    int64_t* __restrict__ dmeta_next, int64_t* __restrict__ hmeta_next,
+    int64_t* __restrict__ limits_next, int rows_per_wg) {
+  __shared__ long long s_wok[RP_WAVES];
+  __shared__ long long s_wch[RP_WAVES];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave_id = threadIdx.x / WAVE;
+  const int KK = (int)limits[1];
+  const int k = threadIdx.x;
+  bool ok = false;
+  if (k < KK) {
+    const float gain = __int_as_float((int)packed[(size_t)k * 6]);
+    ok = (gain > 0.0f) && (packed[(size_t)k * 6 + 1] >= 0) && isfinite(gain);
+  }
+  long long iok = ok ? 1 : 0;  // inclusive wave scan
+  #pragma unroll
+  for (int d = 1; d < WAVE; d <<= 1) {
+    const long long u = __shfl_up(iok, d, WAVE);
+    if (lane >= d) iok += u;
+  }
+  if (lane == WAVE - 1) s_wok[wave_id] = iok;
+  __syncthreads();
+  long long ok_off = 0, n_split = 0;
+  #pragma unroll
+  for (int w = 0; w < RP_WAVES; ++w) {
+    const long long a = s_wok[w];
+    if (w < wave_id) ok_off += a;
+    n_split += a;
+  }
+  const long long pos = ok_off + iok - 1;
+  long long b_start = 0, b_count = 0, b_g = 0, b_h = 0;
+  long long s_start = 0, s_count = 0, s_g = 0, s_h = 0;
+  long long ch = 0;
+  if (ok) {
+    const long long sumg = dmeta[k], sumh = dmeta[KK + k];
+    const long long start = dmeta[2 * (int64_t)KK + k];
+    const long long count = dmeta[3 * (int64_t)KK + k];
+    const long long lg = packed[(size_t)k * 6 + 4];
+    const long long lh = packed[(size_t)k * 6 + 5];
+    const long long lc = node_left_total[pos];
+    const long long rg = sumg - lg, rh = sumh - lh;
+    const bool build_left = lh <= rh;
+    b_start = build_left ? start : start + lc;
+    b_count = build_left ? lc : count - lc;
+    b_g = build_left ? lg : rg;
+    b_h = build_left ? lh : rh;
+    s_start = build_left ? start + lc : start;
+    s_count = build_left ? count - lc : lc;
+    s_g = build_left ? rg : lg;
+    s_h = build_left ? rh : lh;
+    ch = (b_count + rows_per_wg - 1) / rows_per_wg;
+  }
+  long long ich = ch;
+  #pragma unroll
+  for (int d = 1; d < WAVE; d <<= 1) {
+    const long long u = __shfl_up(ich, d, WAVE);
+    if (lane >= d) ich += u;
+  }
+  if (lane == WAVE - 1) s_wch[wave_id] = ich;
+  __syncthreads();
+  long long ch_off = 0, total_chunks = 0;
+  #pragma unroll
+  for (int w = 0; w < RP_WAVES; ++w) {
+    const long long b = s_wch[w];
+    if (w < wave_id) ch_off += b;
+    total_chunks += b;
+  }
+  const long long Kn = n_split, KKn = 2 * n_split;
+  if (ok) {
+    dmeta_next[pos] = b_g;
+    dmeta_next[Kn + pos] = s_g;
+    dmeta_next[KKn + pos] = b_h;
+    dmeta_next[KKn + Kn + pos] = s_h;
+    dmeta_next[2 * KKn + pos] = b_start;
+    dmeta_next[2 * KKn + Kn + pos] = s_start;
+    dmeta_next[3 * KKn + pos] = b_count;
+    dmeta_next[3 * KKn + Kn + pos] = s_count;
+    dmeta_next[4 * KKn + pos] = k;
+    dmeta_next[4 * KKn + Kn + pos] = pos;
+    hmeta_next[pos] = b_start;
+    hmeta_next[Kn + pos] = b_count;
+    hmeta_next[2 * Kn + pos] = ch_off + ich - ch;
+  }
+  if (threadIdx.x == 0) {
+    hmeta_next[3 * Kn] = total_chunks;
+    limits_next[0] = Kn;
+    limits_next[1] = KKn;
+    limits_next[2] = total_chunks;
+  }
+}
+
+// The root's metadata in the same layouts, from the device-resident
+// gradient sums: one node, segment [0, n_local). Also copies the sums to
+// `root_out` so they reach the host with the depth-0 pull.
+__global__ void plan_root_kernel(const int64_t* __restrict__ root_sum,
+                                 int64_t n_local, int rows_per_wg,
+                                 int64_t* __restrict__ dmeta,
+                                 int64_t* __restrict__ hmeta,
+                                 int64_t* __restrict__ limits,
+                                 int64_t* __restrict__ root_out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const int64_t chunks = (n_local + rows_per_wg - 1) / rows_per_wg;
+  dmeta[0] = root_sum[0];
+  dmeta[1] = root_sum[1];
+  dmeta[2] = 0;
+  dmeta[3] = n_local;
+  hmeta[0] = 0;
+  hmeta[1] = n_local;
+  hmeta[2] = 0;
+  hmeta[3] = chunks;
+  limits[0] = 1;
+  limits[1] = 1;
+  limits[2] = chunks;
+  root_out[0] = root_sum[0];
+  root_out[1] = root_sum[1];
+}
+
 static void launch_plan(torch::Tensor packed, torch::Tensor starts_ord,
                         torch::Tensor counts_ord, torch::Tensor meta,
                         torch::Tensor scalars, int K) {
@@ -2392,11 +2644,59 @@ static std::vector<torch::Tensor> reduce_plan_impl(
                        counts_ord.data_ptr<int64_t>(),
                        reinterpret_cast<long long*>(packed.data_ptr<int64_t>()),
                        meta.data_ptr<int64_t>(), scalars.data_ptr<int64_t>(),
-                       K, F);
+                       K, F, (const int64_t*)nullptr, (const int64_t*)nullptr);
   } else {
     launch_reduce(kf, packed, K, F);
     launch_plan(packed, starts_ord, counts_ord, meta, scalars, K);
   }
+  return {packed, meta, scalars, pullbuf};
+}
+
+// reduce_plan_kernel in its device-limit form: K_bound (<= 1024) sizes the
+// outputs, the true frontier size is limits[1] and the node segments come
+// from the scan meta `dmeta`, both device-resident. The outputs keep
+// K_bound-based offsets: packed rows at [6k, 6k+6), the left totals at
+// pullbuf[6 * K_bound ...). Returns {packed, meta, scalars, pullbuf}.
+std::vector<torch::Tensor> reduce_plan_limits(
+    torch::Tensor kf_gain, torch::Tensor kf_bin, torch::Tensor kf_dl,
+    torch::Tensor kf_lg, torch::Tensor kf_lh, torch::Tensor dmeta,
+    torch::Tensor limits, int64_t K_bound) {
+  TORCH_CHECK(K_bound >= 1 && K_bound <= RP_THREADS,
+              "reduce_plan_limits: frontier bound must be in [1, 1024]");
+  const int64_t KF = kf_gain.numel();
+  TORCH_CHECK(KF > 0 && KF % K_bound == 0, "kf arrays must hold K_bound*F entries");
+  const int F = (int)(KF / K_bound);
+  TORCH_CHECK(kf_gain.scalar_type() == torch::kFloat64 &&
+                  kf_bin.scalar_type() == torch::kInt32 &&
+                  kf_dl.scalar_type() == torch::kUInt8 &&
+                  kf_lg.scalar_type() == torch::kInt64 &&
+                  kf_lh.scalar_type() == torch::kInt64 &&
+                  dmeta.scalar_type() == torch::kInt64 &&
+                  limits.scalar_type() == torch::kInt64,
+              "reduce_plan_limits: wrong dtype");
+  for (const auto& t : {kf_gain, kf_bin, kf_dl, kf_lg, kf_lh})
+    TORCH_CHECK(on_gpu(t) && t.is_contiguous() && t.numel() == KF,
+                "kf arrays must be contiguous device tensors of K_bound*F entries");
+  TORCH_CHECK(on_gpu(dmeta) && on_gpu(limits) && dmeta.is_contiguous() &&
+                  limits.numel() >= 3 && dmeta.numel() >= 4 * K_bound,
+              "reduce_plan_limits: need device limits[3], dmeta[>= 4K]");
+  auto optsl =
+      torch::TensorOptions().dtype(torch::kInt64).device(kf_gain.device());
+  auto meta = torch::empty({6 * K_bound + 2}, optsl);
+  auto pullbuf = torch::empty({7 * K_bound}, optsl);
+  auto packed = pullbuf.narrow(0, 0, 6 * K_bound).view({K_bound, 6});
+  auto scalars = torch::empty({2}, optsl);
+  auto stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(reduce_plan_kernel, dim3(1), dim3(RP_THREADS), 0,
+                     stream.stream(), kf_gain.data_ptr<double>(),
+                     kf_bin.data_ptr<int32_t>(), kf_dl.data_ptr<uint8_t>(),
+                     reinterpret_cast<const long long*>(kf_lg.data_ptr<int64_t>()),
+                     reinterpret_cast<const long long*>(kf_lh.data_ptr<int64_t>()),
+                     (const int64_t*)nullptr, (const int64_t*)nullptr,
+                     reinterpret_cast<long long*>(packed.data_ptr<int64_t>()),
+                     meta.data_ptr<int64_t>(), scalars.data_ptr<int64_t>(),
+                     (int)K_bound, F, limits.data_ptr<int64_t>(),
+                     dmeta.data_ptr<int64_t>());
   return {packed, meta, scalars, pullbuf};
 }
 
@@ -2428,7 +2728,7 @@ static std::vector<torch::Tensor> partition_planned(
     torch::Tensor bins, torch::Tensor ridx, torch::Tensor packed,
     torch::Tensor meta, torch::Tensor scalars, torch::Tensor pullbuf,
     torch::Tensor gseg, torch::Tensor bins_t, int64_t chunk_bound,
-    torch::Tensor ridx_dest, bool fused) {
+    torch::Tensor ridx_dest, bool fused, bool stage_pull = true) {
   const int K = (int)packed.size(0);     // frontier bound (scan-slot count)
   auto dev = bins.device();
   // ping-pong destination: the caller tracks which buffer each leaf
@@ -2487,17 +2787,22 @@ static std::vector<torch::Tensor> partition_planned(
   // overlaps the scatter (the first version synced past the scatter,
   // which serialized the bookkeeping after it and measured slower
   // than the 2-sync structure)
-  static thread_local PinnedStager pull_stager;
-  auto pull = pull_stager.get(7 * (int64_t)K);
-  if (pullbuf.defined()) {
-    pull.copy_(pullbuf, /*non_blocking=*/true);
-  } else {
-    pull.narrow(0, 0, 6 * (int64_t)K)
-        .copy_(packed.view({-1}), /*non_blocking=*/true);
-    pull.narrow(0, 6 * (int64_t)K, K)
-        .copy_(node_left_total, /*non_blocking=*/true);
+  // (stage_pull false: the whole-tree enqueue copies pullbuf into its own
+  // per-depth pinned slot instead of this shared one)
+  torch::Tensor pull;
+  if (stage_pull) {
+    static thread_local PinnedStager pull_stager;
+    pull = pull_stager.get(7 * (int64_t)K);
+    if (pullbuf.defined()) {
+      pull.copy_(pullbuf, /*non_blocking=*/true);
+    } else {
+      pull.narrow(0, 0, 6 * (int64_t)K)
+          .copy_(packed.view({-1}), /*non_blocking=*/true);
+      pull.narrow(0, 6 * (int64_t)K, K)
+          .copy_(node_left_total, /*non_blocking=*/true);
+    }
+    pull_stager.mark(stream.stream());
   }
-  pull_stager.mark(stream.stream());
   auto cb = torch::full({1}, chunk_bound, torch::kInt64);
   return {ridx_out, gseg_out, pull, meta, scalars, left_before,
           node_left_total, flags, cb};
@@ -3686,7 +3991,7 @@ std::vector<torch::Tensor> depth_step(
   if (fused_glue) {
     auto kf = find_splits_kf(hist, pg, ph, fb, scale_g, scale_h, lam, alpha,
                              gamma, mcw, mono, bounds, allowed, d_prev,
-                             d_pslots, d_spos);
+                             d_pslots, d_spos, c10::nullopt, c10::nullopt);
     st = partition_rows_from_kf(bins, ridx, d_starts, d_counts, kf[0], kf[1],
                                 kf[2], kf[3], kf[4], gseg, bins_t,
                                 chunk_bound, ridx_dest);
@@ -3706,6 +4011,233 @@ std::vector<torch::Tensor> depth_step(
   partition_scatter_planned(ridx, st[0], gseg, st[1], st[3], st[4], st[5],
                             st[6], st[7], chunk_bound);
   return {st[0], st[1], st[2]};
+}
+
+// ---------------------------------------------------------------------------
+// Whole-tree enqueue: every level of a depthwise tree goes onto the stream
+// in one call, with no host round trip between depths. Depth d+1's
+// launches read their frontier from what plan_next_depth_kernel wrote at
+// depth d; grids are host-known BOUNDS (frontier <= 2^d, histogram chunks
+// <= ceil(n / rows_per_wg) + built nodes, partition chunks <=
+// ceil(n / PART_CHUNK) + frontier) and excess workgroups exit on the
+// device limits. Each depth's {packed | left totals} record is copied to
+// its own pinned slot and followed by its own event, so the host replays
+// depth d's bookkeeping behind the GPU while deeper levels run. The last
+// level runs histogram, scan, reduce and pull only (row-order finish).
+// A depth whose frontier emptied runs as empty launches.
+// ---------------------------------------------------------------------------
+#define TREE_ENQUEUE_MAX_DEPTH 10  // frontier bound 2^9 <= RP_THREADS
+
+struct TreeEnqueueState {
+  torch::Tensor pin;            // [2 root sums | depth 0: 7 | depth 1: 14 ..]
+  std::vector<hipEvent_t> ev;   // one per depth
+};
+static thread_local TreeEnqueueState g_tree_enq;
+
+// {histogram flavour has the limits form (0/1), its rows per workgroup}
+std::vector<int64_t> tree_enqueue_config(torch::Tensor bins, int64_t n_bins) {
+  if (!on_gpu(bins) || bins.dim() != 2) return {0, 0};
+  const HistConfig hc = hist_config(bins, n_bins, 0, bins.size(1), 1);
+  return {hc.xcd ? 1 : 0, hc.rows_per_wg};
+}
+
+// test entry: one plan_next_depth_kernel launch. Outputs are sized for the
+// largest next frontier (every node splits) and pre-filled with -1.
+std::vector<torch::Tensor> plan_next_depth(torch::Tensor packed,
+                                           torch::Tensor dmeta,
+                                           torch::Tensor limits,
+                                           torch::Tensor node_left_total,
+                                           int64_t rows_per_wg) {
+  const int64_t KKb = packed.size(0);
+  TORCH_CHECK(on_gpu(packed) && on_gpu(dmeta) && on_gpu(limits) &&
+                  on_gpu(node_left_total) && packed.is_contiguous() &&
+                  dmeta.is_contiguous() && packed.dim() == 2 &&
+                  packed.size(1) == 6 && KKb >= 1 && KKb <= RP_THREADS &&
+                  packed.scalar_type() == torch::kInt64 &&
+                  dmeta.scalar_type() == torch::kInt64 &&
+                  limits.scalar_type() == torch::kInt64 &&
+                  node_left_total.scalar_type() == torch::kInt64 &&
+                  limits.numel() >= 3 && dmeta.numel() >= 4 * KKb &&
+                  node_left_total.numel() >= KKb && rows_per_wg >= 1,
+              "plan_next_depth: bad arguments");
+  auto optsl = torch::TensorOptions().dtype(torch::kInt64).device(packed.device());
+  auto dm_n = torch::full({10 * KKb}, -1, optsl);
+  auto hm_n = torch::full({3 * KKb + 1}, -1, optsl);
+  auto lim_n = torch::full({3}, -1, optsl);
+  auto stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(plan_next_depth_kernel, dim3(1), dim3(RP_THREADS), 0,
+                     stream.stream(),
+                     reinterpret_cast<const long long*>(packed.data_ptr<int64_t>()),
+                     dmeta.data_ptr<int64_t>(), limits.data_ptr<int64_t>(),
+                     node_left_total.data_ptr<int64_t>(),
+                     dm_n.data_ptr<int64_t>(), hm_n.data_ptr<int64_t>(),
+                     lim_n.data_ptr<int64_t>(), (int)rows_per_wg);
+  return {dm_n, hm_n, lim_n};
+}
+
+// test entry: the XCD histogram kernel in its device-limit form. hist's
+// leading size bounds the built-node count, chunk_bound the row chunks.
+torch::Tensor build_histogram_limits(torch::Tensor bins, torch::Tensor gseg,
+                                     torch::Tensor ridx, torch::Tensor hmeta,
+                                     torch::Tensor limits, int64_t n_bins,
+                                     torch::Tensor hist, int64_t chunk_bound) {
+  const int F = (int)bins.size(1);
+  const int Kb = (int)hist.size(0);
+  const HistConfig hc = hist_config(bins, n_bins, 0, F, Kb);
+  TORCH_CHECK(hc.xcd, "build_histogram_limits: only the XCD flavour has the "
+                      "device-limit form");
+  TORCH_CHECK(on_gpu(bins) && on_gpu(gseg) && on_gpu(ridx) && on_gpu(hmeta) &&
+                  on_gpu(limits) && on_gpu(hist) && hist.is_contiguous() &&
+                  hist.dim() == 4 && hist.size(1) == F &&
+                  hist.size(2) == n_bins && hist.size(3) == 2 &&
+                  hmeta.scalar_type() == torch::kInt64 &&
+                  limits.scalar_type() == torch::kInt64 &&
+                  limits.numel() >= 3 && hmeta.numel() >= 3 * (int64_t)Kb + 1 &&
+                  gseg.scalar_type() == torch::kInt32 &&
+                  ridx.scalar_type() == torch::kInt32 && chunk_bound >= 0,
+              "build_histogram_limits: bad arguments");
+  auto stream = c10::hip::getCurrentHIPStream();
+  launch_hist_xcd(hc, bins, (const int2*)gseg.data_ptr<int32_t>(),
+                  ridx.data_ptr<int32_t>(), hmeta.data_ptr<int64_t>(), nullptr,
+                  reinterpret_cast<long long*>(hist.data_ptr<int64_t>()), Kb,
+                  (int)n_bins, 0, F, chunk_bound, limits.data_ptr<int64_t>(),
+                  stream.stream());
+  return hist;
+}
+
+void tree_enqueue_wait(int64_t depth) {
+  TORCH_CHECK(depth >= 0 && depth < (int64_t)g_tree_enq.ev.size(),
+              "tree_enqueue_wait: no such depth");
+  CHECK_HIP(hipEventSynchronize(g_tree_enq.ev[depth]));
+}
+
+// Returns the pinned record buffer: [sumg, sumh of the root | depth 0's
+// 7 entries | depth 1's 14 | ...]; depth d's slot starts at
+// 2 + 7 * (2^d - 1), holds packed rows at [6k, 6k+6) and the left totals
+// (compact split order) from 6 * 2^d on, and is valid once
+// tree_enqueue_wait(d) returns. The root sums are valid with depth 0.
+torch::Tensor tree_enqueue(
+    torch::Tensor bins, torch::Tensor bins_t, torch::Tensor gseg,
+    torch::Tensor ridx_a, torch::Tensor ridx_b, torch::Tensor root_sum,
+    int64_t max_depth, torch::Tensor fb, double scale_g, double scale_h,
+    double lam, double alpha, double gamma, double mcw, int64_t n_bins) {
+  const int D = (int)max_depth;
+  const int F = (int)bins.size(1);
+  const int64_t n_local = ridx_a.numel();
+  TORCH_CHECK(D >= 1 && D <= TREE_ENQUEUE_MAX_DEPTH,
+              "tree_enqueue: max_depth must be in [1, 10]");
+  TORCH_CHECK(on_gpu(bins) && bins.dtype() == torch::kUInt8 &&
+                  on_gpu(gseg) && gseg.scalar_type() == torch::kInt32 &&
+                  gseg.is_contiguous() && gseg.dim() == 2 &&
+                  gseg.size(0) == n_local && gseg.size(1) == 2 &&
+                  on_gpu(ridx_a) && on_gpu(ridx_b) &&
+                  ridx_a.scalar_type() == torch::kInt32 &&
+                  ridx_b.scalar_type() == torch::kInt32 &&
+                  ridx_b.numel() == n_local && n_local > 0 &&
+                  ridx_a.data_ptr() != ridx_b.data_ptr() &&
+                  on_gpu(root_sum) && root_sum.scalar_type() == torch::kInt64 &&
+                  root_sum.numel() == 2 && root_sum.is_contiguous() &&
+                  on_gpu(fb) && fb.scalar_type() == torch::kInt32 &&
+                  fb.numel() == F && fb.is_contiguous(),
+              "tree_enqueue: bad arguments");
+  const HistConfig hc = hist_config(bins, n_bins, 0, F, 1);
+  TORCH_CHECK(hc.xcd, "tree_enqueue: the selected histogram flavour has no "
+                      "device-limit form");
+  auto dev = bins.device();
+  auto stream = c10::hip::getCurrentHIPStream();
+  auto optsl = torch::TensorOptions().dtype(torch::kInt64).device(dev);
+  const int rows = hc.rows_per_wg;
+
+  auto& S = g_tree_enq;
+  const int64_t total = 2 + 7 * (((int64_t)1 << D) - 1);
+  if (!S.pin.defined() || S.pin.numel() < total)
+    S.pin = torch::empty({total}, torch::TensorOptions()
+                                      .dtype(torch::kInt64)
+                                      .pinned_memory(true));
+  while ((int)S.ev.size() < D) {
+    hipEvent_t e = nullptr;
+    CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    S.ev.push_back(e);
+  }
+
+  // at most two bound-sized histograms live: depth d in buffer d & 1,
+  // its parent level in the other
+  int64_t hn[2] = {0, 0};
+  for (int d = 0; d < D; ++d) hn[d & 1] = (int64_t)1 << d;
+  torch::Tensor hb[2];
+  for (int p = 0; p < 2; ++p)
+    if (hn[p]) hb[p] = torch::empty({hn[p], F, n_bins, 2}, optsl);
+
+  auto e64 = torch::empty({0}, optsl);
+  auto mono = torch::empty({0}, optsl.dtype(torch::kInt8));
+  auto bounds = torch::empty({0, 2}, optsl.dtype(torch::kFloat64));
+  auto allowed = torch::empty({0}, optsl.dtype(torch::kUInt8));
+
+  auto dm = torch::empty({5}, optsl);
+  auto hm = torch::empty({4}, optsl);
+  auto lim = torch::empty({3}, optsl);
+  auto root_out = torch::empty({2}, optsl);
+  hipLaunchKernelGGL(plan_root_kernel, dim3(1), dim3(1), 0, stream.stream(),
+                     root_sum.data_ptr<int64_t>(), n_local, rows,
+                     dm.data_ptr<int64_t>(), hm.data_ptr<int64_t>(),
+                     lim.data_ptr<int64_t>(), root_out.data_ptr<int64_t>());
+  S.pin.narrow(0, 0, 2).copy_(root_out, /*non_blocking=*/true);
+
+  torch::Tensor cur_r = ridx_a, other_r = ridx_b, cur_g = gseg;
+  for (int d = 0; d < D; ++d) {
+    const int64_t KKb = (int64_t)1 << d;        // frontier bound
+    const int64_t Kb = d ? KKb / 2 : 1;         // built-node bound
+    const bool last = d == D - 1;
+    auto hist = hb[d & 1].narrow(0, 0, KKb);
+    hist.narrow(0, 0, Kb).zero_();  // one fill over the bound
+    launch_hist_xcd(hc, bins, (const int2*)cur_g.data_ptr<int32_t>(),
+                    cur_r.data_ptr<int32_t>(), hm.data_ptr<int64_t>(), nullptr,
+                    reinterpret_cast<long long*>(hist.data_ptr<int64_t>()),
+                    (int)Kb, (int)n_bins, 0, F, ceil_div(n_local, rows) + Kb,
+                    lim.data_ptr<int64_t>(), stream.stream());
+    OptTensor prev;
+    if (d) prev = hb[(d - 1) & 1].narrow(0, 0, KKb / 2);
+    auto kf = find_splits_kf(hist, e64, e64, fb, scale_g, scale_h, lam, alpha,
+                             gamma, mcw, mono, bounds, allowed, prev,
+                             c10::nullopt, c10::nullopt, lim, dm);
+    auto rp = reduce_plan_limits(kf[0], kf[1], kf[2], kf[3], kf[4], dm, lim,
+                                 KKb);
+    auto slot = S.pin.narrow(0, 2 + 7 * (KKb - 1), 7 * KKb);
+    if (last) {
+      slot.narrow(0, 0, 6 * KKb)
+          .copy_(rp[3].narrow(0, 0, 6 * KKb), /*non_blocking=*/true);
+      CHECK_HIP(hipEventRecord(S.ev[d], stream.stream()));
+      break;
+    }
+    const int64_t cb = ceil_div(n_local, PART_CHUNK) + KKb;
+    auto st = partition_planned(bins, cur_r, rp[0], rp[1], rp[2], rp[3], cur_g,
+                                bins_t, cb, other_r, /*fused=*/true,
+                                /*stage_pull=*/false);
+    auto dm_n = torch::empty({10 * KKb}, optsl);
+    auto hm_n = torch::empty({3 * KKb + 1}, optsl);
+    auto lim_n = torch::empty({3}, optsl);
+    hipLaunchKernelGGL(plan_next_depth_kernel, dim3(1), dim3(RP_THREADS), 0,
+                       stream.stream(),
+                       reinterpret_cast<const long long*>(rp[0].data_ptr<int64_t>()),
+                       dm.data_ptr<int64_t>(), lim.data_ptr<int64_t>(),
+                       st[6].data_ptr<int64_t>(), dm_n.data_ptr<int64_t>(),
+                       hm_n.data_ptr<int64_t>(), lim_n.data_ptr<int64_t>(),
+                       rows);
+    // the pull and its event go BEFORE the scatter: the host's replay of
+    // this depth overlaps it
+    slot.copy_(rp[3], /*non_blocking=*/true);
+    CHECK_HIP(hipEventRecord(S.ev[d], stream.stream()));
+    partition_scatter_planned(cur_r, st[0], cur_g, st[1], st[3], st[4], st[5],
+                              st[6], st[7], cb);
+    other_r = cur_r;
+    cur_r = st[0];
+    cur_g = st[1];
+    dm = dm_n;
+    hm = hm_n;
+    lim = lim_n;
+  }
+  CHECK_HIP(hipGetLastError());
+  return S.pin.narrow(0, 0, total);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -3733,7 +4265,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lam"), py::arg("alpha"), py::arg("gamma"), py::arg("mcw"),
         py::arg("mono"), py::arg("bounds"), py::arg("allowed"),
         py::arg("prev_hist") = py::none(), py::arg("pslots") = py::none(),
-        py::arg("spos") = py::none());
+        py::arg("spos") = py::none(), py::arg("limits") = py::none(),
+        py::arg("dmeta") = py::none());
+  m.def("reduce_plan_limits", &reduce_plan_limits,
+        "reduce+plan kernel with a device-resident frontier size");
+  m.def("build_histogram_limits", &build_histogram_limits,
+        "XCD histogram kernel with device-resident node and chunk counts");
+  m.def("plan_next_depth", &plan_next_depth,
+        "next depth's scan/histogram metadata from this depth's splits");
+  m.def("tree_enqueue_config", &tree_enqueue_config,
+        "{histogram flavour supports the tree enqueue, rows per workgroup}");
+  m.def("tree_enqueue", &tree_enqueue,
+        "enqueue every level of a depthwise tree without host round trips");
+  m.def("tree_enqueue_wait", &tree_enqueue_wait,
+        "host wait for one depth's pull of the last tree_enqueue");
   m.def("reduce_plan_fused", &reduce_plan_fused,
         "per-node best split + partition plan, one kernel at K <= 1024");
   m.def("reduce_plan_legacy", &reduce_plan_legacy,

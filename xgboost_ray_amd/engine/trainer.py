@@ -183,6 +183,19 @@ class _TreeArrays:
         self.cap = cap
 
 
+def _unpack_splits(pk):
+    """Columns of a pulled ``packed`` [K, 6] int64 block (f32 gain bits,
+    feature, bin, default_left, left_g, left_h) as owned arrays."""
+    return (
+        pk[:, 0].astype(np.int32).view(np.float32).copy(),
+        pk[:, 1].astype(np.int32),
+        pk[:, 2].astype(np.int32),
+        pk[:, 3].astype(np.uint8),
+        pk[:, 4].copy(),
+        pk[:, 5].copy(),
+    )
+
+
 def _calc_weight_vec(G, H, lam, alpha):
     """Vectorized _calc_weight with the identical operation order (the
     scalar path's results are part of the bitwise determinism contract)."""
@@ -907,6 +920,7 @@ class BoostingEngine:
         self._leaf_segs = []
         self._leaf_nids = []
         if self.p.grow_policy == "lossguide":
+            self.last_tree_path = "lossguide"
             return self._grow_tree_lossguide(gq, scale_g, scale_h, it, cls, ptree)
         ridx = self._sample_rows(it, cls + 101 * ptree)
         # segment-ordered gradient pairs aligned with ridx; the partition
@@ -949,8 +963,6 @@ class BoostingEngine:
         fr_nid = np.zeros(1, np.int64)
         fr_start = np.zeros(1, np.int64)
         fr_count = np.array([n_local], np.int64)
-        fr_sumg = np.array([int(root_sum[0])], np.int64)
-        fr_sumh = np.array([int(root_sum[1])], np.int64)
         fr_pslot = np.zeros(1, np.int64)
         fr_wlo = np.full(1, -np.inf)
         fr_whi = np.full(1, np.inf)
@@ -997,6 +1009,60 @@ class BoostingEngine:
         cur_buf = 0
         if use_fused_loop:
             ridx_bufs = [ridx, torch.empty_like(ridx)]
+        # whole-tree enqueue (GPU, per tree like its neighbours): ONE call
+        # puts every level's launches on the stream - depth d+1 reads its
+        # frontier from what a device kernel planned at depth d - and the
+        # loop below only replays each depth's bookkeeping from that
+        # depth's pinned pull, behind the GPU. Taken only where no
+        # per-depth host input exists (no monotone / interaction
+        # constraints, no per-level or per-node column sampling, single
+        # process) and the frontier bound 2^depth fits the single-
+        # workgroup plan kernels. RXGB_TREE_ENQUEUE=0 restores the
+        # per-depth loop exactly.
+        tree_enq = (
+            use_fused_loop and row_finish and fused_glue
+            and _os2.environ.get("RXGB_TREE_ENQUEUE", "1") != "0"
+            and _os2.environ.get("RXGB_DEPTH_STEP") != "1"
+            and not self.coll.is_distributed
+            and self.mono is None
+            and self.interaction_sets is None
+            and self.p.colsample_bylevel >= 1.0
+            and self.p.colsample_bynode >= 1.0
+            and 1 <= self.p.max_depth <= 10
+            and n_local > 0
+        )
+        if tree_enq:
+            from xgboost_ray_amd.ops import gpu as _gpu
+
+            tree_enq = bool(_gpu._load().tree_enqueue_config(
+                self.dtrain.bins, self.n_bins)[0])
+        self.last_tree_path = "enqueue" if tree_enq else "per_depth"
+        enq_pull = None
+        if tree_enq:
+            # the root sums stay on the device and ride the depth-0 pull
+            fr_sumg = np.zeros(1, np.int64)
+            fr_sumh = np.zeros(1, np.int64)
+            fb_tree = self.feat_bins
+            if feat_mask is not None:
+                fb_tree = torch.where(
+                    feat_mask, self.feat_bins,
+                    torch.zeros_like(self.feat_bins),
+                )
+            bins_t_t = getattr(self.dtrain, "bins_t", None)
+            if bins_t_t is None:
+                bins_t_t = torch.zeros(0, dtype=torch.uint8,
+                                       device=self.device)
+            enq_pull = _gpu._load().tree_enqueue(
+                self.dtrain.bins, bins_t_t, gseg, ridx_bufs[0],
+                ridx_bufs[1], root_sum,
+                self.p.max_depth,
+                fb_tree.to(self.device).to(torch.int32).contiguous(),
+                scale_g, scale_h, self.p.reg_lambda, self.p.reg_alpha,
+                self.p.gamma, self.p.min_child_weight, self.n_bins,
+            ).numpy()
+        else:
+            fr_sumg = np.array([int(root_sum[0])], np.int64)
+            fr_sumh = np.array([int(root_sum[1])], np.int64)
 
         lam = float(self.p.reg_lambda)
         alpha = float(self.p.reg_alpha)
@@ -1049,7 +1115,7 @@ class BoostingEngine:
             if self.p.colsample_bylevel < 1.0:
                 lvl_mask = self._sample_features(it, cls, level=depth)
                 mask = lvl_mask if mask is None else (mask & lvl_mask)
-            if mask is not None:
+            if mask is not None and not tree_enq:
                 fb = torch.where(
                     mask, self.feat_bins, torch.zeros_like(self.feat_bins)
                 )
@@ -1067,7 +1133,8 @@ class BoostingEngine:
                 )
 
             F = self.dtrain.n_features
-            all_hist = torch.empty(
+            # (the whole-tree enqueue owns its two ping-pong histograms)
+            all_hist = None if tree_enq else torch.empty(
                 (nF, F, self.n_bins, 2), dtype=torch.int64, device=self.device
             )
 
@@ -1090,7 +1157,27 @@ class BoostingEngine:
                 row_finish and not use_depth_step
                 and depth == self.p.max_depth - 1
             )
-            if use_depth_step:
+            if tree_enq:
+                # everything is already on the stream: wait for THIS
+                # depth's pull (its own pinned slot and event) and replay
+                # it while the GPU runs the deeper levels
+                _gpu._load().tree_enqueue_wait(depth)
+                KKb = 1 << depth  # the slot is laid out on the bound
+                if depth == 0:
+                    fr_sumg[0] = sumg_ord[0] = enq_pull[0]
+                    fr_sumh[0] = sumh_ord[0] = enq_pull[1]
+                arr = enq_pull[2 + 7 * (KKb - 1): 2 + 7 * (2 * KKb - 1)]
+                pk = arr[: 6 * KK].reshape(KK, 6)
+                gain, bfeat, bbin, bdl, blg, blh = _unpack_splits(pk)
+                use_fused = not last_level
+                lc_full = None
+                if use_fused:
+                    lc_full = arr[6 * KKb: 6 * KKb + KK].copy()
+                    depth_in_buf = cur_buf
+                    cur_buf = 1 - cur_buf
+                _tick("scan_pull")
+                return_to_decode = True
+            elif use_depth_step:
                 # one C++ call per depth: stage + zero + hist + derive +
                 # scan + device-planned partition + pull + scatter. The
                 # ~30 per-depth python/torch dispatches were ~0.8 ms of
@@ -1154,12 +1241,7 @@ class BoostingEngine:
                 _gpu._load().wait_pull_event()
                 arr = pull[: 7 * KK].numpy()
                 pk = arr[: 6 * KK].reshape(KK, 6)
-                gain = pk[:, 0].astype(np.int32).view(np.float32).copy()
-                bfeat = pk[:, 1].astype(np.int32)
-                bbin = pk[:, 2].astype(np.int32)
-                bdl = pk[:, 3].astype(np.uint8)
-                blg = pk[:, 4].copy()
-                blh = pk[:, 5].copy()
+                gain, bfeat, bbin, bdl, blg, blh = _unpack_splits(pk)
                 lc_full = arr[6 * KK : 7 * KK].copy()
                 use_fused = True
                 _tick("scan_pull")
@@ -1302,12 +1384,7 @@ class BoostingEngine:
                     pull_ev.synchronize()
                     arr = pull[: 7 * KK].numpy()
                     pk = arr[: 6 * KK].reshape(KK, 6)
-                    gain = pk[:, 0].astype(np.int32).view(np.float32).copy()
-                    bfeat = pk[:, 1].astype(np.int32)
-                    bbin = pk[:, 2].astype(np.int32)
-                    bdl = pk[:, 3].astype(np.uint8)
-                    blg = pk[:, 4].copy()
-                    blh = pk[:, 5].copy()
+                    gain, bfeat, bbin, bdl, blg, blh = _unpack_splits(pk)
                     lc_full = arr[6 * KK : 7 * KK].copy()
                     _tick("scan_pull")
                 else:
@@ -1585,6 +1662,9 @@ class BoostingEngine:
             print("PROF", {k: round(v*1000, 2) for k, v in _t.items()}, flush=True)
         return tree
 
+    # which loop grew the last tree: "enqueue" (whole-tree enqueue),
+    # "per_depth" or "lossguide"
+    last_tree_path: Optional[str] = None
     _leaf_segs: List[Tuple[int, int, float]] = []
     _leaf_nids: List[int] = []  # node id of each _leaf_segs entry
 

@@ -92,12 +92,9 @@ def bench_leaf_quantile(n=11_000_000, K=256, F=28, n_round=2_000_000):
         per_round["reg:quantileerror"] / per_round["reg:squarederror"]))
 
 
-def bench_tree_shap(n=1_000_000, F=28, rounds=100, depth=8,
-                    n_inter=65_536, n_host=64):
-    """Path-form TreeSHAP: contributions of n rows and interactions of
-    n_inter rows through ``rounds`` trees of depth ``depth``, against
-    predict_trees on the same input and against the host recursion
-    (``booster._tree_shap``) on n_host of the rows."""
+def _trained_forest(n, F, rounds, depth):
+    """n x F normal rows on the device and ``rounds`` trees of depth
+    ``depth`` trained on them."""
     from xgboost_ray_amd.engine.trainer import BoostingEngine
 
     dev = torch.device("cuda")
@@ -111,7 +108,17 @@ def bench_tree_shap(n=1_000_000, F=28, rounds=100, depth=8,
         BinnedMatrix.build(X, label=y, max_bin=256))
     for _ in range(rounds):
         eng.update()
-    bst = eng.booster
+    return X, eng.booster
+
+
+def bench_tree_shap(n=1_000_000, F=28, rounds=100, depth=8,
+                    n_inter=65_536, n_host=64):
+    """Path-form TreeSHAP: contributions of n rows and interactions of
+    n_inter rows through ``rounds`` trees of depth ``depth``, against
+    predict_trees on the same input and against the host recursion
+    (``booster._tree_shap``) on n_host of the rows."""
+    dev = torch.device("cuda")
+    X, bst = _trained_forest(n, F, rounds, depth)
     paths = ops.cpu.shap_paths(bst.trees, 1.0)
     lens = np.diff(paths["path_ptr"]).astype(np.int64)
     print(f"forest: {len(bst.trees)} trees, {len(lens)} paths, "
@@ -165,9 +172,124 @@ def bench_tree_shap(n=1_000_000, F=28, rounds=100, depth=8,
           f"{t_host / n_host * 16384 / t_route:.0f} x the device route")
 
 
+def _clock(fn, reps=3):
+    """Median wall time of ``fn`` in seconds (host code, copies included)."""
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return sorted(ts)[len(ts) // 2]
+
+
+def bench_walk(modes=("predict_leaf", "saabas"), n=1_000_000, F=28,
+               rounds=100, depth=8, n_host=65_536, n_route=16_384):
+    """``ops.predict_leaf`` and ``ops.saabas_contribs`` on the shape and
+    model of ``bench_tree_shap`` (output kept on the device), against
+    predict_trees on the same rows, against the numpy walks on the first
+    n_host rows, and the public route at n_route rows with the device route
+    on and off."""
+    dev = torch.device("cuda")
+    X, bst = _trained_forest(n, F, rounds, depth)
+    walk = bst._flatten_for_walk(range(len(bst.trees)))
+    T = len(bst.trees)
+    forest = [walk[k] for k in ("feat", "thr", "left", "default_left")]
+    print(f"forest: {T} trees, {len(walk['feat'])} nodes, largest tree "
+          f"{int(np.diff(walk['tree_ptr'].numpy()).max())} nodes")
+    flat = bst._flat_trees(dev)
+    margin = torch.zeros(n, device=dev)
+    t_pred = timeit("predict_trees", lambda: ops.predict_trees(
+        X, flat["feat"], flat["thr"], flat["left"], flat["default_left"],
+        flat["value"], flat["tree_ptr"], margin))
+    Xh = X[:n_host].cpu().numpy()
+    Xr = np.ascontiguousarray(Xh[:n_route])
+
+    def route(**kw):
+        """Public route at n_route rows, RXGB_WALK_GPU unset and 0."""
+        _os.environ.pop("RXGB_WALK_GPU", None)
+        bst.predict(Xr, **kw)  # builds the cached forest
+        t_dev = _clock(lambda: bst.predict(Xr, **kw))
+        _os.environ["RXGB_WALK_GPU"] = "0"
+        t_np = _clock(lambda: bst.predict(Xr, **kw))
+        t_np_host = _clock(lambda: bst.predict(Xh, **kw), reps=1)
+        _os.environ.pop("RXGB_WALK_GPU", None)
+        print(f"  Booster.predict {n_route} rows: device route "
+              f"{t_dev * 1e3:.1f} ms, numpy route {t_np * 1e3:.1f} ms "
+              f"({t_np / t_dev:.1f} x); numpy route on {n_host} rows "
+              f"{t_np_host:.2f} s ({n_host / t_np_host / 1e3:.1f} k rows/s)")
+
+    if "predict_leaf" in modes:
+        row_bytes = 4 * F + 4 * T
+        out = torch.zeros((n, T), dtype=torch.int32, device=dev)
+        scratch = torch.zeros((T, n), dtype=torch.int32, device=dev)
+
+        def direct():
+            ops.predict_leaf(X, *forest, walk["tree_ptr"], out)
+
+        def tree_major():
+            # coalesced stores into a [T, n] buffer, then a transposing copy
+            ops.predict_leaf(X, *forest, walk["tree_ptr"], scratch.t())
+            out.copy_(scratch.t())
+
+        for label, fn in (("predict_leaf [n,T] stores", direct),
+                          ("predict_leaf [T,n]+transp", tree_major)):
+            t = timeit(label, fn, reps=10)
+            print(f"  {n / t / 1e3:8.1f} M rows/s, {row_bytes} B/row -> "
+                  f"{n * row_bytes / t / 1e6:7.1f} GB/s, "
+                  f"{t / t_pred:.2f} x predict_trees")
+        route(pred_leaf=True)
+
+    if "saabas" in modes:
+        row_bytes = 4 * F + 2 * 8 * (F + 1)
+        out = torch.zeros((n, F + 1), dtype=torch.float64, device=dev)
+
+        def run(label, **kw):
+            t = timeit(label, lambda: ops.saabas_contribs(
+                X, *forest, walk["node_mean"], walk["tree_ptr"], out, **kw),
+                reps=5)
+            print(f"  {n / t / 1e3:8.1f} M rows/s, {row_bytes} B/row -> "
+                  f"{n * row_bytes / t / 1e6:7.1f} GB/s, "
+                  f"{t / t_pred:.2f} x predict_trees")
+            return t
+
+        t_def = run("saabas default")
+        for threads in (64, 128, 256, 384, 512, 576, 640):
+            for tile in (512, 1024, 2048, 4096):
+                lds = 24 * tile + 8 * (F + 1) * threads
+                if lds > ops.gpu.SAABAS_LDS_BYTES:
+                    continue
+                per_cu = min(ops.gpu.SAABAS_LDS_BYTES // lds,
+                             2048 // threads)
+                run(f"saabas {threads}thr tile{tile}", block_threads=threads,
+                    tile_nodes=tile)
+                print(f"    LDS {lds / 1024:.0f} KiB, {per_cu} workgroups = "
+                      f"{per_cu * threads // 64} waves per CU")
+        run("saabas global sums", lds_accumulators=False)
+        run("saabas global 512thr 1024", lds_accumulators=False,
+            block_threads=512, tile_nodes=1024)
+        _os.environ["RXGB_PREDICT_LDS"] = "0"
+        for threads in (256, 512, 1024):
+            run(f"saabas plain {threads}thr", block_threads=threads)
+        run("saabas plain global sums", lds_accumulators=False)
+        _os.environ.pop("RXGB_PREDICT_LDS")
+        paths = ops.cpu.shap_paths(bst.trees, 1.0)
+        exact = torch.zeros((n, 1, F + 1), dtype=torch.float64, device=dev)
+        t_exact = timeit("tree_shap (exact)", lambda: ops.tree_shap(
+            X, paths, 1, exact), reps=1)
+        print(f"  exact / approx on {n} rows: {t_exact / t_def:.0f} x")
+        route(pred_contribs=True, approx_contribs=True)
+        t_exact_r = _clock(lambda: bst.predict(Xr, pred_contribs=True))
+        print(f"  Booster.predict(pred_contribs) exact, {n_route} rows: "
+              f"{t_exact_r * 1e3:.1f} ms")
+
+
 def main():
     if _sys.argv[1:2] == ["leaf_quantile"]:
         return bench_leaf_quantile()
+    if _sys.argv[1:2] in (["predict_leaf"], ["saabas"]):
+        return bench_walk(modes=(_sys.argv[1],))
+    if _sys.argv[1:2] == ["walk"]:
+        return bench_walk()
     if _sys.argv[1:2] == ["tree_shap"]:
         return bench_tree_shap()
     n, F = 11_000_000, 28

@@ -48,7 +48,8 @@ def main():
 
     if torch.cuda.is_available():
         # >= 16384 rows: exact TreeSHAP of the whole matrix on the GPU
-        # (the path-form HIP kernel; RXGB_SHAP_GPU=0 keeps it on the CPU)
+        # (the path-form HIP kernel; RXGB_SHAP_GPU=0 keeps it on the CPU;
+        # pred_leaf / approx_contribs batches: RXGB_WALK_GPU)
         mean_abs = np.abs(bst.predict(X, pred_contribs=True)[:, :5]).mean(0)
         print("mean |SHAP| over all rows:", np.round(mean_abs, 3))
     leaves = bst.predict(rows, pred_leaf=True)

@@ -284,10 +284,11 @@ class _ActorWorker:
         it_range = kwargs.get("iteration_range")
         if kwargs.get("pred_leaf") or kwargs.get("pred_contribs"):
             # leaf-index / SHAP modes run per shard through Booster.predict:
-            # pred_leaf is the CPU tree walk; pred_contribs shards of
-            # >= 16384 rows run the path-form TreeSHAP kernel on this
-            # actor's GPU (smaller ones, or RXGB_SHAP_GPU=0, the CPU
-            # recursion)
+            # shards of >= 16384 rows run on this actor's GPU - pred_leaf
+            # and approx_contribs the tree-walk kernels (RXGB_WALK_GPU=0:
+            # the numpy walks), exact pred_contribs the path-form TreeSHAP
+            # kernel (RXGB_SHAP_GPU=0: the CPU recursion); smaller shards
+            # stay on the CPU
             if shard.get("streaming"):
                 parts = [
                     bst.predict(chunk["data"], **kwargs)

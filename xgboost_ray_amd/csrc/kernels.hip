@@ -15,6 +15,8 @@
 //     binned matrix, leaf value added into the margin (the tree finish)
 //   - grad_fused:     fused objective gradient + |g|/|h| block maxes
 //   - predict_trees:  packed-node tree walk (LDS tree-tiled serving path)
+//   - predict_leaf / saabas_contribs: the same walk writing leaf indices /
+//                     Saabas attributions (float64 sums in an LDS column)
 //   - tree_shap:      exact TreeSHAP contributions / interactions in path
 //     form, float64, one row per thread (no atomics)
 //
@@ -3062,6 +3064,31 @@ __global__ __launch_bounds__(256) void predict_trees_lds_kernel(
   }
 }
 
+// RXGB_PREDICT_LDS=0 sends every tree walk to its plain (global-node)
+// variant, so both variants can be exercised on small forests.
+static bool predict_lds_enabled() {
+  if (const char* e = getenv("RXGB_PREDICT_LDS")) return atoi(e) != 0;
+  return true;
+}
+
+// Greedy tiling of a forest for the LDS tree walks: consecutive trees
+// whose nodes fit `tile_nodes` share a tile; `tiles` receives the tree
+// index each tile starts at (plus T). False when one tree alone exceeds
+// a tile - the caller then takes its plain variant.
+static bool greedy_tree_tiles(const int32_t* tp, int T, int tile_nodes,
+                              std::vector<int32_t>& tiles) {
+  tiles.assign(1, 0);
+  int t = 0;
+  while (t < T) {
+    int t_end = t;
+    while (t_end < T && tp[t_end + 1] - tp[t] <= tile_nodes) ++t_end;
+    if (t_end == t) return false;  // one tree > tile
+    tiles.push_back(t_end);
+    t = t_end;
+  }
+  return true;
+}
+
 void predict_trees(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
                    torch::Tensor left, torch::Tensor default_left,
                    torch::Tensor value, torch::Tensor tree_ptr,
@@ -3083,22 +3110,12 @@ void predict_trees(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
   // tree-tiled LDS path: pack trees into <= PRED_TILE_NODES-node tiles
   // (CPU-side scan over tree_ptr; falls back to the plain kernel when a
   // single tree exceeds the tile or when disabled)
-  bool use_lds = true;
-  if (const char* e = getenv("RXGB_PREDICT_LDS")) use_lds = atoi(e) != 0;
   std::vector<int32_t> tiles;
+  bool use_lds = predict_lds_enabled();
   if (use_lds) {
-    auto tp_cpu = tree_ptr.to(torch::kCPU).to(torch::kInt32);
-    auto tp = tp_cpu.accessor<int32_t, 1>();
-    tiles.push_back(0);
-    int t = 0;
-    while (t < T) {
-      int t_end = t;
-      while (t_end < T && tp[t_end + 1] - tp[t] <= PRED_TILE_NODES)
-        ++t_end;
-      if (t_end == t) { use_lds = false; break; }  // one tree > tile
-      tiles.push_back(t_end);
-      t = t_end;
-    }
+    auto tp_cpu = tree_ptr.to(torch::kCPU).to(torch::kInt32).contiguous();
+    use_lds = greedy_tree_tiles(tp_cpu.data_ptr<int32_t>(), T,
+                                PRED_TILE_NODES, tiles);
   }
   if (use_lds) {
     auto tile_t = torch::from_blob(
@@ -3125,6 +3142,316 @@ void predict_trees(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
                      (const uint4*)packed.data_ptr<int32_t>(),
                      tree_ptr.data_ptr<int32_t>(),
                      out.data_ptr<float>(), (float)tree_weight, n, F, T);
+}
+
+// ---------------------------------------------------------------------------
+// predict_leaf / saabas_contribs: the predict_trees walk with something
+// else written per step. Both reuse the packed node (its value slot is
+// unused) and the greedy LDS tiling; LDS_NODES = false is the plain variant
+// that reads nodes from global memory (one tile spanning the forest).
+// tree_ptr arrives on the HOST and the grid covers exactly the rows of the
+// launch: no cap, no grid-stride loop (the wrappers bound the rows of a
+// launch). One thread owns a row from the first tree to the last, no
+// atomics, no cross-lane sums: launches are bitwise repeatable.
+// ---------------------------------------------------------------------------
+// A forest packed and tiled for the walks: made once per op call
+// (walk_pack), used by every row chunk of that call.
+struct WalkForest {
+  torch::Tensor packed, ptr_d, tile_d;
+  int T, n_tiles, tile_nodes;
+  bool lds_nodes;
+};
+
+// Checks the flat arrays against the host tree_ptr, packs the nodes and
+// tiles the forest into tiles of at most `tile_nodes` nodes.
+WalkForest walk_pack(torch::Tensor feat, torch::Tensor thr,
+                     torch::Tensor left, torch::Tensor default_left,
+                     torch::Tensor tree_ptr, int64_t tile_nodes) {
+  const char* op = "walk_pack";
+  TORCH_CHECK(on_gpu(feat) && on_gpu(thr) && on_gpu(left) &&
+              on_gpu(default_left), op, ": tensors must be on the GPU");
+  TORCH_CHECK(tile_nodes >= 1 && tile_nodes <= PRED_TILE_NODES, op,
+              ": tile_nodes must be in [1, ", PRED_TILE_NODES, "]");
+  TORCH_CHECK(!on_gpu(tree_ptr) && tree_ptr.scalar_type() == torch::kInt32 &&
+              tree_ptr.dim() == 1 && tree_ptr.size(0) >= 1 &&
+              tree_ptr.is_contiguous(),
+              op, ": tree_ptr must be a host int32 vector");
+  const int64_t n_nodes = feat.numel();
+  TORCH_CHECK(feat.scalar_type() == torch::kInt32 && feat.is_contiguous() &&
+              thr.scalar_type() == torch::kFloat32 && thr.is_contiguous() &&
+              left.scalar_type() == torch::kInt32 && left.is_contiguous() &&
+              default_left.scalar_type() == torch::kUInt8 &&
+              default_left.is_contiguous() && thr.numel() == n_nodes &&
+              left.numel() == n_nodes && default_left.numel() == n_nodes,
+              op, ": bad forest arrays");
+  const int T = (int)tree_ptr.size(0) - 1;
+  const int32_t* tp = tree_ptr.data_ptr<int32_t>();
+  TORCH_CHECK(tp[0] == 0 && tp[T] == n_nodes, op,
+              ": tree_ptr does not span the node arrays");
+  for (int t = 0; t < T; ++t)
+    TORCH_CHECK(tp[t + 1] > tp[t], op, ": tree ", t, " has no nodes");
+  WalkForest w;
+  w.T = T;
+  w.tile_nodes = (int)tile_nodes;
+  w.lds_nodes = predict_lds_enabled();
+  std::vector<int32_t> tiles;
+  if (w.lds_nodes)
+    w.lds_nodes = greedy_tree_tiles(tp, T, (int)tile_nodes, tiles);
+  if (!w.lds_nodes) tiles = {0, (int32_t)T};
+  w.n_tiles = (int)tiles.size() - 1;
+  auto dev_i32 = [&](const int32_t* src, int64_t len) {
+    return torch::from_blob(const_cast<int32_t*>(src), {len},
+                            torch::TensorOptions().dtype(torch::kInt32))
+        .clone().to(feat.device());
+  };
+  w.ptr_d = dev_i32(tp, T + 1);
+  w.tile_d = dev_i32(tiles.data(), (int64_t)tiles.size());
+  w.packed = torch::empty({n_nodes, 4},
+      torch::TensorOptions().dtype(torch::kInt32).device(feat.device()));
+  if (n_nodes) {
+    auto zeros = torch::zeros({n_nodes},
+        torch::TensorOptions().dtype(torch::kFloat32).device(feat.device()));
+    hipLaunchKernelGGL(pack_nodes_kernel,
+                       dim3((uint32_t)ceil_div(n_nodes, 256)), dim3(256), 0,
+                       c10::hip::getCurrentHIPStream().stream(),
+                       feat.data_ptr<int32_t>(), thr.data_ptr<float>(),
+                       left.data_ptr<int32_t>(),
+                       default_left.data_ptr<uint8_t>(),
+                       zeros.data_ptr<float>(),
+                       (uint4*)w.packed.data_ptr<int32_t>(), n_nodes);
+  }
+  return w;
+}
+
+static void walk_check_X(const char* op, const torch::Tensor& X,
+                         const WalkForest& w) {
+  TORCH_CHECK(on_gpu(X) && X.scalar_type() == torch::kFloat32 &&
+              X.dim() == 2 && X.is_contiguous() &&
+              X.device() == w.packed.device(),
+              op, ": X must be contiguous f32 [n, F] on the forest's GPU");
+}
+
+// out[row, t] = node index (relative to the tree's root) of the leaf the
+// row reaches in tree t. `out` is addressed through both strides, so the
+// same kernel writes row-major [n, T] or a tree-major [T, n] scratch.
+template <bool LDS_NODES>
+__global__ __launch_bounds__(256) void predict_leaf_kernel(
+    const float* __restrict__ X, const uint4* __restrict__ nodes,
+    const int32_t* __restrict__ tree_ptr,
+    const int32_t* __restrict__ tile_ptr, int32_t* __restrict__ out,
+    int64_t row_stride, int64_t tree_stride, int64_t n, int F, int n_tiles) {
+  __shared__ uint4 lds_nodes[LDS_NODES ? PRED_TILE_NODES : 1];
+  const int64_t row0 =
+      (int64_t)blockIdx.x * blockDim.x * PRED_ROWS_PER_THREAD + threadIdx.x;
+  for (int tile = 0; tile < n_tiles; ++tile) {
+    const int t0 = tile_ptr[tile], t1 = tile_ptr[tile + 1];
+    const int nb0 = tree_ptr[t0];
+    const uint4* nd = nodes + nb0;
+    if (LDS_NODES) {
+      const int span = tree_ptr[t1] - nb0;
+      __syncthreads();  // previous walk done before overwriting LDS
+      for (int i = threadIdx.x; i < span; i += blockDim.x)
+        lds_nodes[i] = nodes[nb0 + i];
+      __syncthreads();
+      nd = lds_nodes;
+    }
+    for (int t = t0; t < t1; ++t) {
+      const int rel = tree_ptr[t] - nb0;
+      #pragma unroll
+      for (int r = 0; r < PRED_ROWS_PER_THREAD; ++r) {
+        const int64_t row = row0 + (int64_t)r * blockDim.x;
+        if (row >= n) continue;
+        int idx = 0;
+        uint4 p = nd[rel];
+        while (!(p.x & 0x80000000u)) {
+          const float v = X[row * (int64_t)F + (p.x & 0x3FFFFFFFu)];
+          const bool goleft =
+              isnan(v) ? ((p.x & 0x40000000u) != 0)
+                       : (v < __uint_as_float(p.y));
+          idx = (int)p.z + (goleft ? 0 : 1);
+          p = nd[rel + idx];
+        }
+        out[row * row_stride + t * tree_stride] = idx;
+      }
+    }
+  }
+}
+
+void predict_leaf(torch::Tensor X, const WalkForest& w, torch::Tensor out) {
+  walk_check_X("predict_leaf", X, w);
+  TORCH_CHECK(!w.lds_nodes || w.tile_nodes <= PRED_TILE_NODES,
+              "predict_leaf: forest tiled beyond the LDS tile");
+  const int64_t n = X.size(0);
+  const int T = w.T;
+  TORCH_CHECK(on_gpu(out) && out.scalar_type() == torch::kInt32 &&
+              out.dim() == 2 && out.size(0) == n && out.size(1) == T,
+              "predict_leaf: out must be int32 [n, T] on the GPU");
+  if (n == 0 || T == 0) return;
+  const int64_t blocks = ceil_div(n, 256 * PRED_ROWS_PER_THREAD);
+  TORCH_CHECK(blocks <= 0x7fffffffLL, "predict_leaf: ", n,
+              " rows exceed one launch");
+  auto stream = c10::hip::getCurrentHIPStream();
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(256), 0,
+                       stream.stream(), X.data_ptr<float>(),
+                       (const uint4*)w.packed.data_ptr<int32_t>(),
+                       w.ptr_d.data_ptr<int32_t>(),
+                       w.tile_d.data_ptr<int32_t>(), out.data_ptr<int32_t>(),
+                       out.stride(0), out.stride(1), n, (int)X.size(1),
+                       w.n_tiles);
+  };
+  if (w.lds_nodes) launch(predict_leaf_kernel<true>);
+  else launch(predict_leaf_kernel<false>);
+  CHECK_HIP(hipGetLastError());
+}
+
+// Saabas attributions. Per row and tree, in this order and in float64:
+// out[row, F] += mean[root]; then at every split on the walk
+// out[row, feat] += mean[child] - mean[node]. The row's F+1 sums start
+// from what `out` holds. LDS_ACC keeps them in an LDS column
+// [feature][thread] (bank = lane: conflict-free whatever the feature),
+// loaded from `out` once and stored once, both coalesced; otherwise every
+// add is a read-modify-write of `out` in global memory, in the same order.
+// Dynamic LDS: [tile nodes | tile means] if LDS_NODES, then accumulators.
+#define SAABAS_LDS_BYTES (160 * 1024)
+template <bool LDS_NODES, bool LDS_ACC>
+__global__ __launch_bounds__(1024) void saabas_contribs_kernel(
+    const float* __restrict__ X, const uint4* __restrict__ nodes,
+    const double* __restrict__ node_mean,
+    const int32_t* __restrict__ tree_ptr,
+    const int32_t* __restrict__ tile_ptr, double* __restrict__ out,
+    int64_t out_stride, int64_t n, int F, int n_tiles, int tile_nodes) {
+  extern __shared__ __attribute__((aligned(16))) char saabas_smem[];
+  uint4* lds_nodes = (uint4*)saabas_smem;
+  double* lds_mean = (double*)(saabas_smem + (size_t)tile_nodes * 16);
+  double* lds_acc =
+      (double*)(saabas_smem + (LDS_NODES ? (size_t)tile_nodes * 24 : 0));
+  const int W = F + 1;
+  const int64_t row_base = (int64_t)blockIdx.x * blockDim.x;
+  const int64_t row = row_base + threadIdx.x;
+  const bool valid = row < n;
+  const int cells =
+      (int)(n - row_base < blockDim.x ? n - row_base : blockDim.x) * W;
+  if (LDS_ACC) {
+    for (int e = threadIdx.x; e < cells; e += blockDim.x) {
+      const int r = e / W, f = e - r * W;
+      lds_acc[f * blockDim.x + r] = out[(row_base + r) * out_stride + f];
+    }
+    __syncthreads();
+  }
+  // the cell of feature f of this thread's row
+  double* acc = LDS_ACC ? lds_acc + threadIdx.x : out + row * out_stride;
+  const int64_t acc_stride = LDS_ACC ? (int64_t)blockDim.x : 1;
+  for (int tile = 0; tile < n_tiles; ++tile) {
+    const int t0 = tile_ptr[tile], t1 = tile_ptr[tile + 1];
+    const int nb0 = tree_ptr[t0];
+    const uint4* nd = nodes + nb0;
+    const double* mn = node_mean + nb0;
+    if (LDS_NODES) {
+      const int span = tree_ptr[t1] - nb0;
+      __syncthreads();  // previous walk done before overwriting LDS
+      for (int i = threadIdx.x; i < span; i += blockDim.x) {
+        lds_nodes[i] = nodes[nb0 + i];
+        lds_mean[i] = node_mean[nb0 + i];
+      }
+      __syncthreads();
+      nd = lds_nodes;
+      mn = lds_mean;
+    }
+    if (!valid) continue;
+    for (int t = t0; t < t1; ++t) {
+      int cur = tree_ptr[t] - nb0;
+      const int rel = cur;
+      uint4 p = nd[cur];
+      double m = mn[cur];
+      acc[F * acc_stride] = acc[F * acc_stride] + m;
+      while (!(p.x & 0x80000000u)) {
+        const int f = (int)(p.x & 0x3FFFFFFFu);
+        const float v = X[row * (int64_t)F + f];
+        const bool goleft =
+            isnan(v) ? ((p.x & 0x40000000u) != 0)
+                     : (v < __uint_as_float(p.y));
+        cur = rel + (int)p.z + (goleft ? 0 : 1);
+        const double mc = mn[cur];
+        acc[f * acc_stride] = acc[f * acc_stride] + (mc - m);
+        m = mc;
+        p = nd[cur];
+      }
+    }
+  }
+  if (LDS_ACC) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < cells; e += blockDim.x) {
+      const int r = e / W, f = e - r * W;
+      out[(row_base + r) * out_stride + f] = lds_acc[f * blockDim.x + r];
+    }
+  }
+}
+
+// lds_acc: -1 = LDS accumulators when they fit SAABAS_LDS_BYTES next to the
+// node tile, 0 = accumulate in global `out`, 1 = LDS or an error.
+// threads (and the forest's tile size): launch geometry, chosen by ops.gpu
+// (defaults measured there; benchmarks sweep them).
+void saabas_contribs(torch::Tensor X, const WalkForest& w,
+                     torch::Tensor node_mean, torch::Tensor out,
+                     int64_t lds_acc, int64_t threads) {
+  TORCH_CHECK(threads >= 64 && threads <= 1024 && threads % 64 == 0,
+              "saabas_contribs: threads must be a multiple of 64 in "
+              "[64, 1024]");
+  walk_check_X("saabas_contribs", X, w);
+  const int64_t tile_nodes = w.tile_nodes;
+  const int64_t n = X.size(0);
+  const int F = (int)X.size(1);
+  const int T = w.T;
+  TORCH_CHECK(on_gpu(node_mean) &&
+              node_mean.scalar_type() == torch::kFloat64 &&
+              node_mean.is_contiguous() && node_mean.numel() == w.packed.size(0),
+              "saabas_contribs: node_mean must be f64 [n_nodes] on the GPU");
+  TORCH_CHECK(on_gpu(out) && out.scalar_type() == torch::kFloat64 &&
+              out.dim() == 2 && out.size(0) == n && out.size(1) == F + 1 &&
+              (n == 0 || out.stride(1) == 1) &&
+              (n <= 1 || out.stride(0) >= F + 1),
+              "saabas_contribs: out must be f64 [n, F+1] on the GPU with "
+              "unit column stride");
+  if (n == 0 || T == 0) return;
+  const size_t node_bytes = w.lds_nodes ? (size_t)tile_nodes * 24 : 0;
+  const size_t acc_bytes = (size_t)(F + 1) * 8 * (size_t)threads;
+  const bool fits = node_bytes + acc_bytes <= SAABAS_LDS_BYTES;
+  TORCH_CHECK(lds_acc != 1 || fits, "saabas_contribs: ", F + 1,
+              " accumulators of ", threads, " threads do not fit the LDS");
+  const bool use_acc = lds_acc == 0 ? false : fits;
+  const size_t lds_bytes = node_bytes + (use_acc ? acc_bytes : 0);
+  const int64_t blocks = ceil_div(n, threads);
+  TORCH_CHECK(blocks <= 0x7fffffffLL, "saabas_contribs: ", n,
+              " rows exceed one launch");
+  auto stream = c10::hip::getCurrentHIPStream();
+  auto launch = [&](auto kernel, bool& attr_set) {
+    if (!attr_set) {
+      // dynamic LDS above 64 KiB needs the opt-in attribute (160 KiB/CU)
+      CHECK_HIP(hipFuncSetAttribute(
+          reinterpret_cast<const void*>(kernel),
+          hipFuncAttributeMaxDynamicSharedMemorySize, SAABAS_LDS_BYTES));
+      attr_set = true;
+    }
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks),
+                       dim3((uint32_t)threads), lds_bytes, stream.stream(),
+                       X.data_ptr<float>(),
+                       (const uint4*)w.packed.data_ptr<int32_t>(),
+                       node_mean.data_ptr<double>(),
+                       w.ptr_d.data_ptr<int32_t>(),
+                       w.tile_d.data_ptr<int32_t>(), out.data_ptr<double>(),
+                       out.stride(0), n, F, w.n_tiles, (int)tile_nodes);
+  };
+  static bool attr_set[4] = {false, false, false, false};
+  if (w.lds_nodes && use_acc)
+    launch(saabas_contribs_kernel<true, true>, attr_set[0]);
+  else if (w.lds_nodes)
+    launch(saabas_contribs_kernel<true, false>, attr_set[1]);
+  else if (use_acc)
+    launch(saabas_contribs_kernel<false, true>, attr_set[2]);
+  else
+    launch(saabas_contribs_kernel<false, false>, attr_set[3]);
+  CHECK_HIP(hipGetLastError());
 }
 
 // ---------------------------------------------------------------------------
@@ -4313,6 +4640,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wait_pull_event", &wait_pull_event,
         "host wait for the depth_step pull event");
   m.def("predict_trees", &predict_trees, "tree-walk prediction");
+  py::class_<WalkForest>(m, "WalkForest")
+      .def_readonly("lds_nodes", &WalkForest::lds_nodes)
+      .def_readonly("tile_nodes", &WalkForest::tile_nodes);
+  m.def("walk_pack", &walk_pack,
+        "pack and tile a forest for predict_leaf / saabas_contribs");
+  m.def("predict_leaf", &predict_leaf, "tree-walk leaf indices");
+  m.def("saabas_contribs", &saabas_contribs,
+        "tree-walk Saabas attributions, accumulated into out",
+        py::arg("X"), py::arg("forest"), py::arg("node_mean"),
+        py::arg("out"), py::arg("lds_acc"), py::arg("threads"));
+  m.attr("PRED_TILE_NODES") = PRED_TILE_NODES;
+  m.attr("SAABAS_LDS_BYTES") = SAABAS_LDS_BYTES;
   m.def("tree_shap", &tree_shap,
         "path-form exact TreeSHAP (contributions or interactions)");
   m.attr("SHAP_TILE_ELEMS") = SHAP_TILE_ELEMS;

@@ -750,6 +750,7 @@ class BoostingEngine:
             t.value *= new_scale
         self.margin += (new_scale - 1.0) * delta
         self.booster._flat_cache = None
+        self.booster._walk_cache = None  # node means follow the leaf values
         # scale the dropped trees and re-add their shrunk contribution
         for ti in dropped:
             self.booster.trees[ti].value *= old_scale

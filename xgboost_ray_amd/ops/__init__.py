@@ -238,6 +238,56 @@ def predict_trees(
     )
 
 
+def predict_leaf(X, feat, thr, left, default_left, tree_ptr, out, **kw):
+    """Leaf reached by every row in every tree of a forest slice.
+
+    X: fp32 [n, F] raw features (NaN = missing). The forest is the flat SoA
+    of ``predict_trees`` without ``value``; ``tree_ptr`` is an int32 [T+1]
+    HOST vector. out: int32 [n, T], overwritten with the node index of the
+    leaf reached in tree t, relative to ``tree_ptr[t]`` (0 for a tree
+    whose root is a leaf) - the index ``Booster.predict_leaf`` and xgboost
+    return. Decision rule exactly as in ``predict_trees``: left iff
+    x < thr in float32, NaN follows default_left, right child = left + 1.
+    A forest whose walk could leave its arrays (split feature >= F,
+    children outside their tree or not after their parent) is a
+    ValueError.
+
+    Dispatches on X's device. On the GPU ``out`` may live on the host or
+    be strided: rows are processed in chunks whose device output stays
+    under ``max_out_bytes`` (keyword, default ``ops.gpu.WALK_OUT_BYTES``),
+    each chunk copied out before the next one runs.
+    """
+    return _impl(X).predict_leaf(
+        X, feat, thr, left, default_left, tree_ptr, out, **kw)
+
+
+def saabas_contribs(X, feat, thr, left, default_left, node_mean, tree_ptr,
+                    out, **kw):
+    """Saabas (approximate) feature contributions, accumulated into ``out``.
+
+    X and the forest as in ``predict_leaf``. node_mean: float64 [n_nodes],
+    the cover-weighted expected value of every node
+    (``booster._fill_node_means``), flattened like the other arrays. out:
+    float64 [n, F+1], unit column stride, any row stride. Per row, for each
+    tree in order: ``out[row, F] = out[row, F] + node_mean[root]``, then for
+    each split on the row's walk from the root down
+    ``out[row, feat] = out[row, feat] + (node_mean[child] - node_mean[node])``.
+    Every operation is an IEEE float64 add or subtract in exactly this
+    sequence, and the sums START from the values ``out`` holds on entry, so
+    the result is bitwise defined and equal on every backend.
+
+    Dispatches on X's device. On the GPU a host ``out`` is processed in row
+    chunks under ``max_out_bytes`` (keyword, default
+    ``ops.gpu.WALK_OUT_BYTES``): each chunk of ``out`` is copied to the
+    device, accumulated into and copied back. ``lds_accumulators``
+    (keyword, GPU): None keeps a row's sums in LDS when F+1 columns fit,
+    False accumulates in global memory, True makes a misfit an error; the
+    result is the same bytes either way.
+    """
+    return _impl(X).saabas_contribs(
+        X, feat, thr, left, default_left, node_mean, tree_ptr, out, **kw)
+
+
 SHAP_MAX_PATH_LEN = _cpu.SHAP_MAX_PATH_LEN
 
 

@@ -288,6 +288,109 @@ def predict_trees(X, feat, thr, left, default_left, value, tree_ptr, out, tree_w
     return out
 
 
+def walk_forest_error(feat, left, tree_ptr, n_features):
+    """Why the tree walks cannot take this forest, or None: an empty
+    tree, a split feature outside ``[0, n_features)``, or a child pair
+    that lies outside its tree or does not come after its parent (every
+    walk then ends, and every index it forms is in range)."""
+    import numpy as np
+
+    feat, left = np.asarray(feat), np.asarray(left)
+    ptr = np.asarray(tree_ptr, dtype=np.int64)
+    if len(ptr) < 1 or ptr[0] != 0 or ptr[-1] != len(feat):
+        return "tree_ptr does not span the node arrays"
+    if len(left) != len(feat):
+        return "forest arrays differ in length"
+    sizes = np.diff(ptr)
+    if (sizes <= 0).any():
+        return "a tree has no nodes"
+    split = feat >= 0
+    if (feat[split] >= n_features).any():
+        return (f"forest splits on feature {int(feat.max())}, X has "
+                f"{n_features} columns")
+    rel = np.arange(len(feat)) - np.repeat(ptr[:-1], sizes)
+    size = np.repeat(sizes, sizes)
+    lc = left[split].astype(np.int64)
+    if ((lc <= rel[split]) | (lc + 1 >= size[split])).any():
+        return "a split's children lie outside its tree or before it"
+    return None
+
+
+def _walk_check(op, X, feat, left, tree_ptr):
+    err = walk_forest_error(_as_numpy(feat), _as_numpy(left),
+                            _as_numpy(tree_ptr), X.shape[1])
+    if err:
+        raise ValueError(f"{op}: {err}")
+
+
+def _walk_levels(X, feat, thr, left, default_left, base):
+    """One tree, level by level: yields (rows still at a split, their node,
+    the child they move to), node indices absolute."""
+    import numpy as np
+
+    cur = np.full(X.shape[0], base, np.int64)
+    rows = np.arange(X.shape[0])
+    while True:
+        rows = rows[feat[cur[rows]] >= 0]
+        if not len(rows):
+            return
+        node = cur[rows]
+        x = X[rows, feat[node]]
+        with np.errstate(invalid="ignore"):
+            go_left = np.where(np.isnan(x), default_left[node] != 0,
+                               x < thr[node])
+        child = base + left[node] + np.where(go_left, 0, 1)
+        yield rows, node, child
+        cur[rows] = child
+
+
+def predict_leaf(X, feat, thr, left, default_left, tree_ptr, out,
+                 max_out_bytes=None):
+    """Numerics oracle of the leaf-index walk (contract: ``ops.predict_leaf``),
+    numpy on the host."""
+    import numpy as np
+
+    _walk_check("predict_leaf", X, feat, left, tree_ptr)
+    Xn, o = _as_numpy(X), _as_numpy(out)
+    arrs = [_as_numpy(a) for a in (feat, thr, left, default_left)]
+    ptr = _as_numpy(tree_ptr)
+    if o.shape != (Xn.shape[0], len(ptr) - 1) or o.dtype != np.int32:
+        raise ValueError("predict_leaf: out must be int32 [n, T]")
+    for t in range(len(ptr) - 1):
+        base = int(ptr[t])
+        o[:, t] = 0
+        for rows, _, child in _walk_levels(Xn, *arrs, base):
+            o[rows, t] = child - base
+    return out
+
+
+def saabas_contribs(X, feat, thr, left, default_left, node_mean, tree_ptr,
+                    out, max_out_bytes=None, lds_accumulators=None):
+    """Numerics oracle of the Saabas walk (contract: ``ops.saabas_contribs``),
+    numpy on the host. A row meets one split per level, so each level's
+    fancy-indexed add touches a cell once and the per-cell order is the
+    tree-then-depth order of the contract."""
+    import numpy as np
+
+    _walk_check("saabas_contribs", X, feat, left, tree_ptr)
+    Xn, o, mean = _as_numpy(X), _as_numpy(out), _as_numpy(node_mean)
+    arrs = [_as_numpy(a) for a in (feat, thr, left, default_left)]
+    ptr = _as_numpy(tree_ptr)
+    F = Xn.shape[1]
+    if o.shape != (Xn.shape[0], F + 1) or o.dtype != np.float64:
+        raise ValueError("saabas_contribs: out must be float64 [n, F+1]")
+    if mean.dtype != np.float64 or mean.shape != arrs[0].shape:
+        raise ValueError("saabas_contribs: node_mean must be float64 "
+                         "[n_nodes]")
+    for t in range(len(ptr) - 1):
+        base = int(ptr[t])
+        o[:, F] = o[:, F] + mean[base]
+        for rows, node, child in _walk_levels(Xn, *arrs, base):
+            f = arrs[0][node]
+            o[rows, f] = o[rows, f] + (mean[child] - mean[node])
+    return out
+
+
 def update_margins(margin, ridx, starts, counts, leaf_values):
     for k in range(len(starts)):
         s, c = int(starts[k]), int(counts[k])

@@ -198,6 +198,105 @@ def predict_trees(X, feat, thr, left, default_left, value, tree_ptr, out, tree_w
     return out
 
 
+# -- leaf indices and Saabas contributions -----------------------------------
+# Rows per launch are bounded: the device output of one launch stays under
+# this size, and the grid of a launch covers exactly its rows.
+WALK_OUT_BYTES = 1 << 30
+# saabas_contribs launch geometry (measured, docs/parity.md). A workgroup's
+# LDS holds one node tile (16 B node + 8 B mean each) and the F+1 float64
+# sums of each of its rows: 8 waves with a 1024-node tile at F <= 33, fewer
+# rows per workgroup for wider inputs. Where not even 64 rows fit, the sums
+# are updated in global memory, which wants few resident rows and big tiles.
+SAABAS_LDS_BYTES = 160 * 1024
+SAABAS_THREADS = 512
+SAABAS_TILE_NODES = 1024
+SAABAS_GLOBAL_GEOMETRY = (256, 4096)
+
+
+def saabas_block_threads(F, tile_nodes=SAABAS_TILE_NODES):
+    """Rows per workgroup for F features: the largest multiple of 64, up to
+    SAABAS_THREADS, whose sums fit in LDS next to a node tile (0: none)."""
+    room = SAABAS_LDS_BYTES - 24 * tile_nodes
+    return min(SAABAS_THREADS, room // (8 * (F + 1)) // 64 * 64)
+
+
+def saabas_lds_max_features():
+    """Largest F whose sums stay in LDS."""
+    return (SAABAS_LDS_BYTES - 24 * SAABAS_TILE_NODES) // (8 * 64) - 1
+
+
+def _walk_pack(op, X, feat, thr, left, default_left, tree_ptr, tile_nodes):
+    """Check the forest and pack it on X's device: once per op call,
+    shared by every row chunk of the call."""
+    from xgboost_ray_amd.ops import cpu
+
+    tree_ptr = torch.as_tensor(tree_ptr).to("cpu", torch.int32).contiguous()
+    err = cpu.walk_forest_error(feat.cpu().numpy(), left.cpu().numpy(),
+                                tree_ptr.numpy(), X.shape[1])
+    if err:
+        raise ValueError(f"{op}: {err}")
+    dev = X.device
+    return _load().walk_pack(
+        feat.to(dev).contiguous(), thr.to(dev).contiguous(),
+        left.to(dev).contiguous(), default_left.to(dev).contiguous(),
+        tree_ptr, int(tile_nodes)), len(tree_ptr) - 1
+
+
+def _row_chunks(n, row_bytes, max_out_bytes):
+    chunk = max(1, int(WALK_OUT_BYTES if max_out_bytes is None
+                       else max_out_bytes) // max(1, row_bytes))
+    return [(s, min(n, s + chunk)) for s in range(0, n, chunk)]
+
+
+def predict_leaf(X, feat, thr, left, default_left, tree_ptr, out,
+                 max_out_bytes=None):
+    dev = X.device
+    X = X.contiguous()
+    forest, T = _walk_pack("predict_leaf", X, feat, thr, left, default_left,
+                           tree_ptr, _load().PRED_TILE_NODES)
+    n = X.shape[0]
+    if tuple(out.shape) != (n, T) or out.dtype != torch.int32:
+        raise ValueError(f"predict_leaf: out must be int32 {(n, T)}")
+    for s, e in _row_chunks(n, 4 * T, max_out_bytes):
+        # the kernel stores through both strides of a device out
+        buf = out[s:e] if out.is_cuda else torch.empty(
+            (e - s, T), dtype=torch.int32, device=dev)
+        _load().predict_leaf(X[s:e], forest, buf)
+        if not out.is_cuda:
+            # copy this chunk out before the next one runs
+            out[s:e] = buf.cpu()
+    return out
+
+
+def saabas_contribs(X, feat, thr, left, default_left, node_mean, tree_ptr,
+                    out, max_out_bytes=None, lds_accumulators=None,
+                    block_threads=None, tile_nodes=None):
+    """``block_threads`` / ``tile_nodes`` override the launch geometry
+    (benchmarks/bench_ops.py sweeps them)."""
+    dev = X.device
+    X = X.contiguous()
+    n, F = X.shape
+    if tuple(out.shape) != (n, F + 1) or out.dtype != torch.float64:
+        raise ValueError(f"saabas_contribs: out must be float64 {(n, F + 1)}")
+    mean = node_mean.to(dev).contiguous()
+    lds_acc = -1 if lds_accumulators is None else int(bool(lds_accumulators))
+    threads, tile = saabas_block_threads(F), SAABAS_TILE_NODES
+    if lds_acc == 0 or (threads == 0 and lds_acc < 0):
+        threads, tile = SAABAS_GLOBAL_GEOMETRY
+    threads = int(block_threads or threads or 64)  # 64: the misfit error
+    forest, _ = _walk_pack("saabas_contribs", X, feat, thr, left,
+                           default_left, tree_ptr, tile_nodes or tile)
+    direct = out.is_cuda and (n == 0 or out.stride(1) == 1)
+    for s, e in _row_chunks(n, 8 * (F + 1), max_out_bytes):
+        # the sums start from what out holds: a chunk that is not
+        # accumulated in place goes to the device first and comes back
+        buf = out[s:e] if direct else out[s:e].to(dev).contiguous()
+        _load().saabas_contribs(X[s:e], forest, mean, buf, lds_acc, threads)
+        if not direct:
+            out[s:e] = buf.to(out.device)
+    return out
+
+
 def lambdarank_grad(margin, label, group_ptr, rank, idcg, use_ndcg):
     return _load().lambdarank_grad(
         margin, label, group_ptr, rank, idcg, bool(use_ndcg)

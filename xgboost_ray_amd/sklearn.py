@@ -71,6 +71,7 @@ class RayXGBMixin:
         ray_params=None,
         _remote=None,
         ray_dmatrix_params=None,
+        pred_leaf=False,
     ):
         ray_params = self._ray_set_ray_params_n_jobs(
             ray_params, getattr(self, "n_jobs", None)
@@ -89,6 +90,7 @@ class RayXGBMixin:
             _remote=_remote,
             output_margin=output_margin,
             iteration_range=iteration_range,
+            **({"pred_leaf": True} if pred_leaf else {}),
         )
 
 
@@ -227,6 +229,17 @@ class _RayXGBModel(RayXGBMixin):
         if self._Booster is None:
             raise ValueError("Model not fitted yet; call fit() first.")
         return self._Booster
+
+    def apply(self, X, iteration_range=None, ray_params=None, _remote=None,
+              ray_dmatrix_params=None):
+        """Leaf index of every row in every tree (xgboost
+        ``XGBModel.apply``): int32 [n, trees], rows in input order, through
+        the distributed ``predict(..., pred_leaf=True)``."""
+        return self._ray_predict(
+            X, iteration_range=iteration_range, ray_params=ray_params,
+            _remote=_remote, ray_dmatrix_params=ray_dmatrix_params,
+            pred_leaf=True,
+        )
 
     def load_model(self, fname):
         self._Booster = Booster()

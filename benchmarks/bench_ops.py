@@ -92,6 +92,107 @@ def bench_leaf_quantile(n=11_000_000, K=256, F=28, n_round=2_000_000):
         per_round["reg:quantileerror"] / per_round["reg:squarederror"]))
 
 
+def bench_mvs(n=11_000_000, F=28, subsample=0.2, rounds=20, depth=8):
+    """Gradient-based sampling: each kernel at n rows with its achieved
+    GB/s over the compulsory bytes, the whole sampler against the
+    host-side uniform one, and a depth-``depth`` binary:logistic round on
+    n x F with no sampling / uniform / gradient_based (training logloss
+    after ``rounds`` rounds next to each)."""
+    from xgboost_ray_amd.engine.trainer import BoostingEngine
+    from xgboost_ray_amd.ops import gpu as gpu_ops
+
+    dev = torch.device("cuda")
+    gen = torch.Generator(device=dev).manual_seed(0)
+
+    def rate(name, fn, nbytes, reps=20):
+        dt = timeit(name, fn, reps=reps)
+        print(f"    achieved {n * nbytes / dt / 1e6:8.1f} GB/s "
+              f"({nbytes} B/row)")
+        return dt
+
+    k = max(1, int(subsample * n))
+    y = (torch.rand(n, device=dev, generator=gen) < 0.4).float()
+    p = torch.sigmoid(2.0 * torch.randn(n, device=dev, generator=gen))
+    # logistic pairs take the closed form (t* > max c); squared-error
+    # pairs with Cauchy-tailed residuals force the four select passes
+    r = torch.tan(3.14159 * (torch.rand(n, device=dev, generator=gen) - 0.5))
+    shapes = (
+        ("logistic", torch.stack([p - y, p * (1 - p)], 1).contiguous()),
+        ("cauchy", torch.stack([r, torch.ones_like(r)], 1).contiguous()),
+    )
+    del p, r
+    for name, gp in shapes:
+        print(f"-- mvs kernels, {name} pairs, n={n}, k={k}")
+        mx = (float(gp[:, 0].abs().max()), float(gp[:, 1].abs().max()))
+        c = ops.mvs_score(gp, *mx)
+        rate("mvs_score", lambda: ops.mvs_score(gp, *mx), 12)
+        rate("mvs_stats", lambda: gpu_ops.mvs_stats(c), 4)
+        S, M = ops.mvs_threshold(c, k)
+        closed = S == int(gpu_ops.mvs_stats(c)[2]) and M == k
+        print(f"    threshold: S={S} M={M} closed_form={closed}")
+        # the select's own prefixes: the leading bytes of t* = S // M
+        t = min(S // M, int(gpu_ops.mvs_stats(c)[1])) if M else 0
+        total = 0.0
+        for ps in range(4):
+            prefix = (t >> (32 - 8 * ps)) if ps else 0
+            total += rate(f"mvs_hist pass{ps}",
+                          lambda: ops.mvs_hist(c, prefix, ps), 4)
+        print(f"    4 passes {total:.3f} ms")
+        timeit("mvs_threshold (pulls)", lambda: ops.mvs_threshold(c, k))
+        rate("mvs_sample", lambda: ops.mvs_sample(gp, c, S, M, 12345), 21)
+        keep, _ = ops.mvs_sample(gp, c, S, M, 12345)
+        print(f"    sample size {int(keep.sum())} (k = {k})")
+        timeit("nonzero -> int32 ridx",
+               lambda: torch.nonzero(keep).flatten().to(torch.int32))
+
+        def sampler():
+            cc = ops.mvs_score(gp, *mx)
+            s, m = ops.mvs_threshold(cc, k)
+            kp, gw = ops.mvs_sample(gp, cc, s, m, 12345)
+            return torch.nonzero(kp).flatten().to(torch.int32), gw
+
+        timeit("whole gradient sampler", sampler)
+        del c, keep
+
+    def uniform_host():
+        g = torch.Generator(device="cpu")
+        g.manual_seed(7)
+        mask = torch.rand(n, generator=g) < subsample
+        return torch.nonzero(mask.to(dev)).flatten().to(torch.int32)
+
+    timeit("host uniform sampler", uniform_host, reps=5)
+    del shapes, gp
+
+    X = torch.randn(n, F, device=dev, generator=gen)
+    y = ((X[:, 0] + 0.5 * X[:, 1]
+          + 0.5 * torch.randn(n, device=dev, generator=gen)) > 0).float()
+    dm = BinnedMatrix.build(X, label=y, max_bin=256)
+    del X
+    print(f"-- rounds, {n} x {F}, depth {depth}, binary:logistic")
+    for name, extra in (
+            ("subsample=1", {}),
+            (f"uniform {subsample}", {"subsample": subsample}),
+            (f"gradient_based {subsample}",
+             {"subsample": subsample, "sampling_method": "gradient_based"})):
+        eng = BoostingEngine(
+            dict({"objective": "binary:logistic", "max_depth": depth,
+                  "eta": 0.3, "tree_method": "gpu_hist", "seed": 0},
+                 **extra), dm)
+        eng.update()
+        eng.update()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(rounds - 2):
+            eng.update()
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / (rounds - 2) * 1000
+        m = eng.margin.double()
+        ll = float((torch.nn.functional.softplus(m) - y.double() * m).mean())
+        print(f"round {name:22s} {dt:9.3f} ms   logloss after {rounds} "
+              f"rounds {ll:.6f}   sample rows {eng.last_sample_rows}",
+              flush=True)
+
+
 def _trained_forest(n, F, rounds, depth):
     """n x F normal rows on the device and ``rounds`` trees of depth
     ``depth`` trained on them."""
@@ -292,6 +393,8 @@ def main():
         return bench_walk()
     if _sys.argv[1:2] == ["tree_shap"]:
         return bench_tree_shap()
+    if _sys.argv[1:2] == ["mvs"]:  # mvs [rows]
+        return bench_mvs(*(int(a) for a in _sys.argv[2:3]))
     n, F = 11_000_000, 28
     dev = torch.device("cuda")
     gen = torch.Generator(device=dev).manual_seed(0)

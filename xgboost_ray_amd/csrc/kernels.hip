@@ -19,6 +19,8 @@
 //                     Saabas attributions (float64 sums in an LDS column)
 //   - tree_shap:      exact TreeSHAP contributions / interactions in path
 //     form, float64, one row per thread (no atomics)
+//   - mvs_score / mvs_stats / mvs_hist / mvs_sample: gradient-based row
+//     sampling, the sample decided in integer arithmetic
 //
 // Design notes (per /opt/skills/guides/cdna_hip_programming.md):
 //   wave = 64 lanes; LDS = 160 KiB/CU; histogram tiles sized so 1-2
@@ -1620,6 +1622,224 @@ __global__ void lambdarank_kernel(
     }
     out[s0 + i] = make_float2((float)gacc, (float)hacc);
   }
+}
+
+// ---------------------------------------------------------------------------
+// Gradient-based row sampling (minimal-variance sampling; the contract is
+// in docs/parity.md "Gradient-based sampling"). Everything that decides
+// WHICH rows are kept is integer arithmetic, so these kernels are
+// array_equal to the ops.cpu oracles:
+//   mvs_score   c = isqrt(rne((g^2 + 0.1 h^2) * sv)), c in [0, 2^30]
+//   mvs_stats   (#{c > 0}, max c, sum c)
+//   mvs_hist    one MSB-first radix pass: per digit (count, sum c)
+//   mvs_sample  keep mask + reweighted pairs from (S, M) and a counter hash
+// Rows are read in identity order (coalesced, no gather). Every launch
+// covers exactly its rows: one row per thread (score, sample) or one
+// MVS_CHUNK per workgroup (stats, hist); no address depends on a gradient
+// value beyond `digit & 255`.
+// ---------------------------------------------------------------------------
+#define MVS_THREADS 256
+#define MVS_ROWS_PER_THREAD 16
+#define MVS_CHUNK (MVS_THREADS * MVS_ROWS_PER_THREAD)
+#define MVS_WAVES (MVS_THREADS / WAVE)
+#define MVS_VMAX (1ll << 60)
+
+__global__ __launch_bounds__(MVS_THREADS) void mvs_score_kernel(
+    const float2* __restrict__ gpair, uint32_t* __restrict__ c, double sv,
+    int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * MVS_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const float2 gp = gpair[i];
+  const double g = (double)gp.x, h = (double)gp.y;
+  // float32 squares are exact in float64; no contraction (build flag)
+  const double v = g * g + 0.1 * (h * h);
+  const double x = v * sv;
+  long long V = MVS_VMAX;  // "not < 2^60" includes NaN
+  if (x < (double)MVS_VMAX) V = llrint(x);
+  if (V < 0) V = 0;
+  // integer square root: start from the float one, then correct, so the
+  // result does not depend on how sqrt (or the int64 -> double step) rounds
+  long long r = (long long)sqrt((double)V);
+  for (int it = 0; it < 4 && r * r > V; ++it) --r;
+  for (int it = 0; it < 4 && (r + 1) * (r + 1) <= V; ++it) ++r;
+  c[i] = (uint32_t)r;
+}
+
+__device__ __forceinline__ unsigned long long mvs_shfl_down_u64(
+    unsigned long long v, int off) {
+  return (unsigned long long)__shfl_down((long long)v, off, WAVE);
+}
+
+// partials[block] = (#{c > 0}, max c, sum c) of the block's chunk; one
+// mvs_stats_fold_kernel block folds them (no same-address global atomics,
+// as in quantize_gpair_kernel)
+__global__ __launch_bounds__(MVS_THREADS) void mvs_stats_kernel(
+    const uint32_t* __restrict__ c, int64_t n,
+    unsigned long long* __restrict__ partials) {  // [gridDim.x, 3]
+  const int64_t row_lo = (int64_t)blockIdx.x * MVS_CHUNK;
+  unsigned long long nz = 0ull, mx = 0ull, sum = 0ull;
+  #pragma unroll
+  for (int s = 0; s < MVS_ROWS_PER_THREAD; ++s) {
+    const int64_t i = row_lo + s * MVS_THREADS + threadIdx.x;
+    if (i < n) {
+      const unsigned long long v = c[i];
+      nz += v != 0ull;
+      mx = v > mx ? v : mx;
+      sum += v;
+    }
+  }
+  #pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    nz += mvs_shfl_down_u64(nz, off);
+    const unsigned long long o = mvs_shfl_down_u64(mx, off);
+    mx = o > mx ? o : mx;
+    sum += mvs_shfl_down_u64(sum, off);
+  }
+  __shared__ unsigned long long part[MVS_WAVES][3];
+  if ((threadIdx.x & (WAVE - 1)) == 0) {
+    part[threadIdx.x / WAVE][0] = nz;
+    part[threadIdx.x / WAVE][1] = mx;
+    part[threadIdx.x / WAVE][2] = sum;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < MVS_WAVES; ++w) {
+      nz += part[w][0];
+      mx = part[w][1] > mx ? part[w][1] : mx;
+      sum += part[w][2];
+    }
+    partials[3 * (size_t)blockIdx.x] = nz;
+    partials[3 * (size_t)blockIdx.x + 1] = mx;
+    partials[3 * (size_t)blockIdx.x + 2] = sum;
+  }
+}
+
+// one block: stats = fold of partials [n_blocks, 3]
+__global__ __launch_bounds__(MVS_THREADS) void mvs_stats_fold_kernel(
+    const unsigned long long* __restrict__ partials, int64_t n_blocks,
+    unsigned long long* __restrict__ stats) {
+  unsigned long long nz = 0ull, mx = 0ull, sum = 0ull;
+  for (int64_t i = threadIdx.x; i < n_blocks; i += MVS_THREADS) {
+    nz += partials[3 * i];
+    const unsigned long long o = partials[3 * i + 1];
+    mx = o > mx ? o : mx;
+    sum += partials[3 * i + 2];
+  }
+  #pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    nz += mvs_shfl_down_u64(nz, off);
+    const unsigned long long o = mvs_shfl_down_u64(mx, off);
+    mx = o > mx ? o : mx;
+    sum += mvs_shfl_down_u64(sum, off);
+  }
+  __shared__ unsigned long long part[MVS_WAVES][3];
+  if ((threadIdx.x & (WAVE - 1)) == 0) {
+    part[threadIdx.x / WAVE][0] = nz;
+    part[threadIdx.x / WAVE][1] = mx;
+    part[threadIdx.x / WAVE][2] = sum;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < MVS_WAVES; ++w) {
+      nz += part[w][0];
+      mx = part[w][1] > mx ? part[w][1] : mx;
+      sum += part[w][2];
+    }
+    stats[0] = nz;
+    stats[1] = mx;
+    stats[2] = sum;
+  }
+}
+
+// hist[digit] += (1, c) over the rows whose top 8*pass bits equal pfx;
+// digit = the next 8 bits. One (count, sum) LDS sub-histogram per wave,
+// non-zero bins flushed with 64-bit global atomics (integer: order-free)
+// into copy blockIdx.x % n_slots of the histogram, which spreads the
+// same-address atomics of the early passes (a whole chunk shares a few
+// digits there); mvs_hist_fold_kernel adds the copies up.
+#define MVS_HIST_SLOTS 32
+__global__ __launch_bounds__(MVS_THREADS) void mvs_hist_kernel(
+    const uint32_t* __restrict__ c, int64_t n, uint32_t pfx, int pass,
+    unsigned long long* __restrict__ slots, int n_slots) {  // [n_slots, 512]
+  unsigned long long* hist = slots + (size_t)(blockIdx.x % n_slots) * 512;
+  __shared__ unsigned long long lds[MVS_WAVES * 512];
+  for (int i = threadIdx.x; i < MVS_WAVES * 512; i += MVS_THREADS)
+    lds[i] = 0ull;
+  const int hi_shift = 32 - 8 * pass;  // bits above the digit (32 in pass 0)
+  const int lo_shift = 24 - 8 * pass;
+  const int64_t row_lo = (int64_t)blockIdx.x * MVS_CHUNK;
+  __syncthreads();
+  unsigned long long* my = lds + (threadIdx.x / WAVE) * 512;
+  #pragma unroll
+  for (int s = 0; s < MVS_ROWS_PER_THREAD; ++s) {
+    const int64_t i = row_lo + s * MVS_THREADS + threadIdx.x;
+    if (i >= n) continue;
+    const uint32_t v = c[i];
+    if (pass != 0 && (v >> hi_shift) != pfx) continue;
+    const uint32_t d = (v >> lo_shift) & 255u;
+    atomicAdd(&my[2 * d], 1ull);
+    if (v != 0u) atomicAdd(&my[2 * d + 1], (unsigned long long)v);
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < 512; b += MVS_THREADS) {
+    unsigned long long v = lds[b];
+    #pragma unroll
+    for (int wv = 1; wv < MVS_WAVES; ++wv) v += lds[wv * 512 + b];
+    if (v != 0ull) atomicAdd(&hist[b], v);
+  }
+}
+
+// one block: hist[b] = sum over the n_slots copies, b in [0, 512)
+__global__ __launch_bounds__(512) void mvs_hist_fold_kernel(
+    const unsigned long long* __restrict__ slots, int n_slots,
+    unsigned long long* __restrict__ hist) {
+  const int b = threadIdx.x;
+  unsigned long long v = 0ull;
+  for (int s = 0; s < n_slots; ++s) v += slots[(size_t)s * 512 + b];
+  hist[b] = v;
+}
+
+__device__ __forceinline__ unsigned long long mvs_splitmix64(
+    unsigned long long z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// keep row i iff c > 0 and (S == 0 or c*M >= S or u*S < (c*M) * 2^32),
+// u = splitmix64(key + i) >> 32. floor(u*S / 2^32) < c*M is that 128-bit
+// comparison (the low 32 bits of u*S cannot lift it past a multiple of
+// 2^32). A row kept with p < 1 is scaled by S / (c*M) in float64.
+__global__ __launch_bounds__(MVS_THREADS) void mvs_sample_kernel(
+    const float2* __restrict__ gpair, const uint32_t* __restrict__ c,
+    unsigned long long S, unsigned long long M, unsigned long long key,
+    uint8_t* __restrict__ keep, float2* __restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * MVS_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long ci = c[i];
+  const float2 gp = gpair[i];
+  float2 o = make_float2(0.f, 0.f);
+  uint8_t k = 0;
+  if (ci != 0ull) {
+    const unsigned long long cm = ci * M;
+    if (S == 0ull || cm >= S) {
+      k = 1;
+      o = gp;
+    } else {
+      const unsigned long long u =
+          mvs_splitmix64(key + (unsigned long long)i) >> 32;
+      const unsigned long long q = (__umul64hi(u, S) << 32) | ((u * S) >> 32);
+      if (q < cm) {
+        k = 1;
+        const double f = (double)(long long)S / (double)(long long)cm;
+        o.x = (float)((double)gp.x * f);
+        o.y = (float)((double)gp.y * f);
+      }
+    }
+  }
+  keep[i] = k;
+  out[i] = o;
 }
 
 // ===========================================================================
@@ -3972,6 +4192,108 @@ void leaf_quantile_hist(torch::Tensor resid, torch::Tensor weight,
                      (long long*)hist.data_ptr<int64_t>(), K, (int)pass);
 }
 
+// -- gradient-based row sampling ---------------------------------------------
+static void mvs_check_c(const torch::Tensor& c) {
+  TORCH_CHECK(on_gpu(c) && c.dtype() == torch::kUInt32 && c.dim() == 1 &&
+                  c.is_contiguous() && c.numel() < (1ll << 31),
+              "mvs: c must be a contiguous uint32 device vector, n < 2^31");
+}
+
+static void mvs_check_gpair(const torch::Tensor& gpair) {
+  TORCH_CHECK(on_gpu(gpair) && gpair.dtype() == torch::kFloat32 &&
+                  gpair.dim() == 2 && gpair.size(1) == 2 &&
+                  gpair.is_contiguous() && gpair.size(0) < (1ll << 31),
+              "mvs: gpair must be contiguous f32 [n, 2] on device, n < 2^31");
+}
+
+torch::Tensor mvs_score(torch::Tensor gpair, double sv) {
+  mvs_check_gpair(gpair);
+  const int64_t n = gpair.size(0);
+  auto c = torch::empty({n}, gpair.options().dtype(torch::kUInt32));
+  if (n == 0) return c;
+  auto stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(mvs_score_kernel,
+                     dim3((uint32_t)ceil_div(n, MVS_THREADS)),
+                     dim3(MVS_THREADS), 0, stream.stream(),
+                     (const float2*)gpair.data_ptr<float>(),
+                     c.data_ptr<uint32_t>(), sv, n);
+  return c;
+}
+
+// int64 [3] device: (#{c > 0}, max c, sum c)
+torch::Tensor mvs_stats(torch::Tensor c) {
+  mvs_check_c(c);
+  const int64_t n = c.numel();
+  const auto opts = c.options().dtype(torch::kInt64);
+  if (n == 0) return torch::zeros({3}, opts);
+  auto stats = torch::empty({3}, opts);  // the fold writes all of it
+  const int64_t blocks = ceil_div(n, MVS_CHUNK);
+  auto partials =
+      torch::empty({blocks, 3}, c.options().dtype(torch::kInt64));
+  auto stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(mvs_stats_kernel, dim3((uint32_t)blocks),
+                     dim3(MVS_THREADS), 0, stream.stream(),
+                     c.data_ptr<uint32_t>(), n,
+                     (unsigned long long*)partials.data_ptr<int64_t>());
+  hipLaunchKernelGGL(mvs_stats_fold_kernel, dim3(1), dim3(MVS_THREADS), 0,
+                     stream.stream(),
+                     (const unsigned long long*)partials.data_ptr<int64_t>(),
+                     blocks, (unsigned long long*)stats.data_ptr<int64_t>());
+  return stats;
+}
+
+// int64 [256, 2] device: per digit (count, sum c) of the rows under prefix
+torch::Tensor mvs_hist(torch::Tensor c, int64_t prefix, int64_t pass) {
+  mvs_check_c(c);
+  TORCH_CHECK(pass >= 0 && pass < 4, "pass must be 0..3");
+  TORCH_CHECK(prefix >= 0 && prefix < (1ll << (8 * pass)),
+              "prefix must fit the top 8*pass bits");
+  const int64_t n = c.numel();
+  const auto opts = c.options().dtype(torch::kInt64);
+  if (n == 0) return torch::zeros({256, 2}, opts);
+  auto hist = torch::empty({256, 2}, opts);  // the fold writes all of it
+  const int64_t blocks = ceil_div(n, MVS_CHUNK);
+  const int n_slots =
+      blocks < MVS_HIST_SLOTS ? (int)blocks : MVS_HIST_SLOTS;
+  auto slots =
+      torch::zeros({n_slots, 512}, c.options().dtype(torch::kInt64));
+  auto stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(mvs_hist_kernel, dim3((uint32_t)blocks),
+                     dim3(MVS_THREADS), 0, stream.stream(),
+                     c.data_ptr<uint32_t>(), n, (uint32_t)prefix, (int)pass,
+                     (unsigned long long*)slots.data_ptr<int64_t>(), n_slots);
+  hipLaunchKernelGGL(mvs_hist_fold_kernel, dim3(1), dim3(512), 0,
+                     stream.stream(),
+                     (const unsigned long long*)slots.data_ptr<int64_t>(),
+                     n_slots, (unsigned long long*)hist.data_ptr<int64_t>());
+  return hist;
+}
+
+// (keep uint8 [n], reweighted gpair f32 [n, 2]); key: the uint64 bits
+std::vector<torch::Tensor> mvs_sample(torch::Tensor gpair, torch::Tensor c,
+                                      int64_t S, int64_t M, int64_t key) {
+  mvs_check_gpair(gpair);
+  mvs_check_c(c);
+  const int64_t n = gpair.size(0);
+  TORCH_CHECK(c.numel() == n, "mvs_sample: c must have one value per row");
+  // c*M < 2^61 and u*S < 2^93: the kernel's products do not wrap
+  TORCH_CHECK(S >= 0 && M >= 0 && S < (1ll << 61) && M < (1ll << 31),
+              "mvs_sample: (S, M) out of range");
+  auto keep = torch::empty({n}, gpair.options().dtype(torch::kUInt8));
+  auto out = torch::empty_like(gpair);
+  if (n == 0) return {keep, out};
+  auto stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(mvs_sample_kernel,
+                     dim3((uint32_t)ceil_div(n, MVS_THREADS)),
+                     dim3(MVS_THREADS), 0, stream.stream(),
+                     (const float2*)gpair.data_ptr<float>(),
+                     c.data_ptr<uint32_t>(), (unsigned long long)S,
+                     (unsigned long long)M, (unsigned long long)key,
+                     keep.data_ptr<uint8_t>(),
+                     (float2*)out.data_ptr<float>(), n);
+  return {keep, out};
+}
+
 torch::Tensor lambdarank_grad(torch::Tensor margin, torch::Tensor label,
                               torch::Tensor group_ptr, torch::Tensor rank,
                               torch::Tensor idcg, bool use_ndcg) {
@@ -4659,5 +4981,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("update_margins", &update_margins, "leaf margin update");
   m.def("leaf_quantile_hist", &leaf_quantile_hist,
         "per-leaf radix-select digit histogram (one pass)");
+  m.def("mvs_score", &mvs_score, "gradient-based sampling: row scores");
+  m.def("mvs_stats", &mvs_stats,
+        "gradient-based sampling: (#nonzero, max, sum) of the scores");
+  m.def("mvs_hist", &mvs_hist,
+        "gradient-based sampling: one radix-select pass over the scores");
+  m.def("mvs_sample", &mvs_sample,
+        "gradient-based sampling: keep mask + reweighted gradient pairs");
   m.def("lambdarank_grad", &lambdarank_grad, "pairwise lambdarank gradients");
 }

@@ -51,6 +51,7 @@ class TrainParams:
     min_child_weight: float = 1.0
     max_delta_step: float = 0.0
     subsample: float = 1.0
+    sampling_method: str = "uniform"  # or "gradient_based"
     num_parallel_tree: int = 1
     colsample_bytree: float = 1.0
     colsample_bylevel: float = 1.0
@@ -104,6 +105,21 @@ class TrainParams:
         p.num_class = int(p.num_class or 0)
         p.seed = int(p.seed or 0)
         p.num_parallel_tree = max(1, int(p.num_parallel_tree or 1))
+        p.subsample = 1.0 if p.subsample is None else float(p.subsample)
+        p.sampling_method = p.sampling_method or "uniform"
+        if not 0.0 < p.subsample <= 1.0:
+            raise ValueError(
+                f"subsample must be in (0, 1], got {p.subsample}")
+        if p.sampling_method not in ("uniform", "gradient_based"):
+            raise ValueError(
+                "sampling_method must be 'uniform' or 'gradient_based', "
+                f"got {p.sampling_method!r}")
+        if (p.sampling_method == "gradient_based"
+                and p.objective == "reg:quantileerror"):
+            raise ValueError(
+                "sampling_method='gradient_based' is not supported with "
+                "reg:quantileerror: adaptive leaves take unweighted "
+                "residual quantiles of the sampled rows")
         if isinstance(p.monotone_constraints, str):
             txt = p.monotone_constraints.strip().strip("()")
             p.monotone_constraints = [
@@ -289,6 +305,10 @@ class BoostingEngine:
         self._adaptive = self.obj.adaptive_alpha(0) is not None
         self._adaptive_resid = None
         self._int_weight_cache = None
+        # gradient-based sampling: the kept rows of the tree being grown
+        # (None: uniform sampling), and the size of the last row sample
+        self._mvs_ridx = None
+        self.last_sample_rows = None
         if self._adaptive and self.p.monotone_constraints and any(
             int(c) for c in self.p.monotone_constraints
         ):
@@ -793,8 +813,44 @@ class BoostingEngine:
             return gq, scale_g, scale_h
         return ops.quantize_gpair(gpair, scale_g, scale_h), scale_g, scale_h
 
+    def _mvs_sample(self, gpair: torch.Tensor, it: int, tree: int):
+        """sampling_method="gradient_based": keep row i with probability
+        ~ sqrt(g^2 + 0.1 h^2), expected sample size k = subsample * n
+        (per rank), and divide a kept row's pair by that probability.
+        Returns the reweighted pairs (dropped rows zero); the ascending
+        kept row ids go to ``_sample_rows`` through ``_mvs_ridx``. Integer
+        arithmetic decides the sample: CPU and GPU draw the same rows."""
+        fused_mx = getattr(gpair, "_rxgb_absmax", None)
+        if fused_mx is not None:
+            mx = fused_mx.double()
+        else:
+            mx = torch.stack(
+                [gpair[:, 0].abs().max(), gpair[:, 1].abs().max()]
+            ).double()
+        if self.coll.is_distributed:
+            mx_d = mx.to(self.device) if self.device.type == "cuda" else mx
+            self.coll.allreduce_(mx_d, op="max")
+            mx = mx_d
+        mx = mx.cpu()
+        k = max(1, int(self.p.subsample * self.dtrain.n_rows))
+        c = ops.mvs_score(gpair, float(mx[0]), float(mx[1]))
+        S, M = ops.mvs_threshold(c, k)
+        keep, gpair_w = ops.mvs_sample(
+            gpair, c, S, M,
+            ops.mvs_key(self.p.seed, it, tree, self.rank),
+        )
+        self._mvs_ridx = torch.nonzero(keep).flatten().to(torch.int32)
+        return gpair_w
+
     def _sample_rows(self, it: int, cls: int) -> torch.Tensor:
+        ridx = self._sample_rows_impl(it, cls)
+        self.last_sample_rows = int(ridx.numel())
+        return ridx
+
+    def _sample_rows_impl(self, it: int, cls: int) -> torch.Tensor:
         n = self.dtrain.n_rows
+        if self._mvs_ridx is not None:
+            return self._mvs_ridx
         if self.p.subsample >= 1.0:
             return torch.arange(n, dtype=torch.int32, device=self.device)
         gen = torch.Generator(device="cpu")
@@ -915,6 +971,12 @@ class BoostingEngine:
             _last[0] = now
 
         _tick(None)
+        self._mvs_ridx = None
+        if (self.p.sampling_method == "gradient_based"
+                and self.p.subsample < 1.0):
+            # sample first: the reweighted pairs are what gets quantised
+            gpair = self._mvs_sample(gpair, it, cls + 101 * ptree)
+            _tick("mvs_sample")
         gq, scale_g, scale_h = self._quantize(gpair)
         _tick("quantize")
         self._scale_g_cur = scale_g

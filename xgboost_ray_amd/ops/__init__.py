@@ -408,6 +408,58 @@ def leaf_quantile_select(resid, weight, ridx, starts, counts, alpha,
     return bits.astype(np.uint32).view(np.float32), W_seg
 
 
+mvs_key = _cpu.mvs_key  # uint64 stream key from (seed, iteration, tree, rank)
+
+
+def mvs_score(gpair, mx_g, mx_h):
+    """Gradient-based sampling, step 1: integer row scores.
+
+    gpair: f32 [n, 2]; mx_g / mx_h: the (global) maxima of |g| and |h|.
+    With sv = 2^60 / max(mx_g^2 + 0.1 mx_h^2, 1e-300) (float64, host), per
+    row in float64 without contraction: v = g*g + 0.1*(h*h),
+    V = rne(v * sv) clamped to 2^60 (NaN clamps too), c = floor(sqrt(V))
+    as an exact integer square root. Returns uint32 [n], c in [0, 2^30];
+    c / 2^30 is sqrt(g^2 + 0.1 h^2) relative to its largest possible value.
+    """
+    return _impl(gpair).mvs_score(gpair, mx_g, mx_h)
+
+
+def mvs_hist(c, prefix, pass_idx):
+    """One MSB-first radix pass over the scores: int64 [256, 2] of
+    (count, sum c) per digit, over the rows whose top ``8 * pass_idx`` bits
+    equal ``prefix`` (digit = the next 8 bits). Integer sums: CPU and GPU
+    agree exactly."""
+    return _impl(c).mvs_hist(c, prefix, pass_idx)
+
+
+def mvs_threshold(c, k):
+    """Gradient-based sampling, step 2: the threshold for an expected
+    sample of k rows, as Python ints (S, M) with mu = S / M.
+
+    With A(t) = sum of c_i < t and N(t) = #{c_i >= t}: (0, 0) if at most k
+    scores are non-zero (keep them all, unweighted). Otherwise t* is the
+    largest integer t >= 1 with A(t) >= (k - N(t)) * t,
+    S = sum of c_i <= t*, M = k - #{c_i > t*}; a row is then kept with
+    probability min(1, c_i * M / S). If t* exceeds max c the answer is the
+    closed form (sum c, k); else t* comes from four ``mvs_hist`` passes,
+    the digit chosen on the host after each.
+    """
+    return _impl(c).mvs_threshold(c, k)
+
+
+def mvs_sample(gpair, c, S, M, key):
+    """Gradient-based sampling, step 3: draw the sample.
+
+    Row i is kept iff c_i > 0 and (S == 0 or c_i*M >= S or
+    u_i*S < c_i*M*2^32) with u_i = splitmix64(key + i) >> 32 (uint64,
+    wrapping) - integer arithmetic only. A row kept with probability < 1
+    gets f32(f64(g) * (f64(S) / f64(c_i*M))) (same for h); one kept for
+    certain keeps its pair; a dropped row gets (0, 0).
+    Returns (keep uint8 [n], gpair_w f32 [n, 2]).
+    """
+    return _impl(gpair).mvs_sample(gpair, c, S, M, key)
+
+
 def grad_fused(margin, label, weight, scale_pos_weight, mode):
     """Fused objective gradient + |g|/|h| max for the hot objectives
     (mode 0 = reg:squarederror, 1 = binary:logistic). GPU only: returns

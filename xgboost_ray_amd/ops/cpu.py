@@ -431,6 +431,167 @@ def leaf_quantile_hist(resid, weight, ridx, starts, counts, prefix, pass_idx,
 
 
 # ---------------------------------------------------------------------------
+# Gradient-based row sampling (minimal-variance sampling)
+# ---------------------------------------------------------------------------
+# Which rows are kept is decided in integer arithmetic only, so these
+# oracles and the HIP kernels agree bit for bit (docs/parity.md).
+MVS_LAMBDA = 0.1  # weight of h^2 in the score, as in xgboost's sampler
+MVS_VMAX = 1 << 60
+_U64 = (1 << 64) - 1
+
+
+def _splitmix64_int(z: int) -> int:
+    z = (z + 0x9E3779B97F4A7C15) & _U64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _U64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _U64
+    return z ^ (z >> 31)
+
+
+def mvs_key(seed: int, iteration: int, tree: int, rank: int) -> int:
+    """uint64 stream key of one tree on one rank. Row i draws
+    ``splitmix64(key + i)``, so the four ingredients are hashed one after
+    the other: keys that differ in any of them are far apart."""
+    key = 0
+    for part in (seed, iteration, tree, rank):
+        key = _splitmix64_int((key + int(part)) & _U64)
+    return key
+
+
+def mvs_scale(mx_g: float, mx_h: float) -> float:
+    """sv = 2^60 / max(mx_g^2 + 0.1 mx_h^2, 1e-300) in float64 (inf when
+    both maxima are zero: every score then clamps to 2^30)."""
+    import numpy as np
+
+    mg, mh = np.float64(mx_g), np.float64(mx_h)
+    with np.errstate(over="ignore", invalid="ignore"):
+        d = mg * mg + np.float64(MVS_LAMBDA) * (mh * mh)
+        return float(np.float64(MVS_VMAX) / max(d, np.float64(1e-300)))
+
+
+def mvs_score(gpair, mx_g, mx_h):
+    """c = isqrt(clamp(rne((g^2 + 0.1 h^2) * sv), 2^60)) as uint32 [n],
+    sv = ``mvs_scale(mx_g, mx_h)``."""
+    import numpy as np
+
+    sv = mvs_scale(mx_g, mx_h)
+    gp = gpair.detach().cpu().numpy().astype(np.float64)
+    g, h = gp[:, 0], gp[:, 1]
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = g * g + np.float64(MVS_LAMBDA) * (h * h)
+        x = v * np.float64(sv)
+        V = np.full(len(x), MVS_VMAX, np.int64)
+        m = x < np.float64(MVS_VMAX)  # False for NaN
+        V[m] = np.rint(x[m]).astype(np.int64)  # half to even
+    V = np.maximum(V, 0)
+    # integer square root: float start, then corrected
+    r = np.sqrt(V.astype(np.float64)).astype(np.int64)
+    for _ in range(4):
+        r -= r * r > V
+    for _ in range(4):
+        r += (r + 1) * (r + 1) <= V
+    return torch.from_numpy(r.astype(np.uint32))
+
+
+def _mvs_c(c):
+    import numpy as np
+
+    return c.detach().cpu().numpy().astype(np.int64)
+
+
+def mvs_stats(c):
+    """int64 [3]: (#{c > 0}, max c, sum c)."""
+    v = _mvs_c(c)
+    if not len(v):
+        return torch.zeros(3, dtype=torch.int64)
+    return torch.tensor(
+        [int((v > 0).sum()), int(v.max()), int(v.sum())], dtype=torch.int64)
+
+
+def mvs_hist(c, prefix, pass_idx):
+    """int64 [256, 2]: per digit (count, sum c) of the rows whose top
+    ``8 * pass_idx`` bits equal ``prefix``; digit = the next 8 bits."""
+    import numpy as np
+
+    v = _mvs_c(c)
+    if pass_idx:
+        v = v[(v >> (32 - 8 * pass_idx)) == int(prefix)]
+    d = (v >> (24 - 8 * pass_idx)) & 255
+    out = np.zeros((256, 2), np.int64)
+    np.add.at(out[:, 0], d, 1)
+    np.add.at(out[:, 1], d, v)
+    return torch.from_numpy(out)
+
+
+def mvs_threshold(c, k, stats=None, hist=None):
+    """(S, M) of the sampling threshold as Python ints - see
+    ``ops.mvs_threshold``. ``stats`` / ``hist`` are the backend's
+    ``mvs_stats`` / ``mvs_hist`` (default: the oracles above); the digit
+    choice after each pass runs here, on the host, in Python ints."""
+    stats = stats or mvs_stats
+    hist = hist or mvs_hist
+    k = int(k)
+    n_pos, mx, total = (int(x) for x in stats(c).cpu().tolist())
+    if n_pos <= k:
+        return 0, 0
+    if total >= k * (mx + 1):
+        # P(max c + 1) holds: t* > max c, every row is below the threshold
+        return total, k
+    # MSB-first radix select of t* = the largest t with
+    # P(t): A(t) >= (k - N(t)) * t. At a candidate t on a digit boundary
+    # A and N follow from the bins below / from the digit on.
+    prefix = 0
+    below_sum = 0  # sum of c over rows below the prefix's range
+    above_cnt = 0  # rows above the prefix's range
+    for p in range(4):
+        h = hist(c, prefix, p).cpu().numpy()
+        cnt, sm = h[:, 0].tolist(), h[:, 1].tolist()
+        shift = 24 - 8 * p
+        a, nn = below_sum, above_cnt + sum(cnt)
+        best = (0, a, nn)  # P holds at the prefix itself (or at t = 0)
+        for d in range(256):
+            t = ((prefix << 8) | d) << shift
+            if a >= (k - nn) * t:
+                best = (d, a, nn)
+            a += sm[d]
+            nn -= cnt[d]
+        d, a_t, n_t = best
+        below_sum = a_t
+        above_cnt = n_t - cnt[d]
+        prefix = (prefix << 8) | d
+    eq = n_t - above_cnt  # rows with c == t*
+    return a_t + eq * prefix, k - above_cnt
+
+
+def mvs_sample(gpair, c, S, M, key):
+    """(keep uint8 [n], reweighted gpair f32 [n, 2]) - see ops.mvs_sample."""
+    import numpy as np
+
+    gp = gpair.detach().cpu().numpy().astype(np.float32)
+    cc = c.detach().cpu().numpy().astype(np.uint64)
+    n = len(cc)
+    S, M = int(S), int(M)
+    with np.errstate(over="ignore"):
+        z = np.arange(n, dtype=np.uint64) + np.uint64(int(key) & _U64)
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    u = z >> np.uint64(32)
+    cm = cc * np.uint64(M)
+    sure = (cc > 0) & (np.bool_(S == 0) | (cm >= np.uint64(S)))
+    # floor(u * S / 2^32) < c * M  <=>  u * S < (c * M) * 2^32
+    q = u * np.uint64(S >> 32) + (
+        (u * np.uint64(S & 0xFFFFFFFF)) >> np.uint64(32))
+    prob = (cc > 0) & ~sure & (q < cm)
+    out = np.zeros((n, 2), np.float32)
+    out[sure] = gp[sure]
+    f = np.float64(S) / cm[prob].astype(np.float64)
+    out[prob] = (gp[prob].astype(np.float64) * f[:, None]).astype(np.float32)
+    keep = (sure | prob).astype(np.uint8)
+    return torch.from_numpy(keep), torch.from_numpy(out)
+
+
+# ---------------------------------------------------------------------------
 # Exact TreeSHAP in path form
 # ---------------------------------------------------------------------------
 # longest root-to-leaf path, counted in UNIQUE features, the path-form ops

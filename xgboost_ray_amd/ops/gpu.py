@@ -345,6 +345,36 @@ def leaf_quantile_hist(resid, weight, ridx, starts, counts, prefix, pass_idx,
     return out
 
 
+# -- gradient-based row sampling ---------------------------------------------
+def mvs_score(gpair, mx_g, mx_h):
+    from xgboost_ray_amd.ops import cpu
+
+    return _load().mvs_score(gpair.contiguous(), cpu.mvs_scale(mx_g, mx_h))
+
+
+def mvs_stats(c):
+    return _load().mvs_stats(c)
+
+
+def mvs_hist(c, prefix, pass_idx):
+    return _load().mvs_hist(c, int(prefix), int(pass_idx))
+
+
+def mvs_threshold(c, k):
+    # the digit choice is the oracle's host code over this backend's kernels
+    from xgboost_ray_amd.ops import cpu
+
+    return cpu.mvs_threshold(c, k, stats=mvs_stats, hist=mvs_hist)
+
+
+def mvs_sample(gpair, c, S, M, key):
+    key = int(key) & ((1 << 64) - 1)
+    if key >= 1 << 63:
+        key -= 1 << 64  # the uint64 bits, passed as int64
+    keep, out = _load().mvs_sample(gpair.contiguous(), c, int(S), int(M), key)
+    return keep, out
+
+
 def grad_fused(margin, label, weight, scale_pos_weight, mode):
     w = weight if weight is not None else torch.zeros(
         0, dtype=torch.float32, device=margin.device)

@@ -22,6 +22,7 @@ _PARAM_NAMES = (
     "min_child_weight",
     "max_delta_step",
     "subsample",
+    "sampling_method",
     "colsample_bytree",
     "colsample_bylevel",
     "colsample_bynode",
@@ -154,6 +155,7 @@ class _RayXGBModel(RayXGBMixin):
         min_child_weight: Optional[float] = None,
         max_delta_step: Optional[float] = None,
         subsample: Optional[float] = None,
+        sampling_method: Optional[str] = None,
         colsample_bytree: Optional[float] = None,
         colsample_bylevel: Optional[float] = None,
         colsample_bynode: Optional[float] = None,
@@ -184,6 +186,7 @@ class _RayXGBModel(RayXGBMixin):
         self.min_child_weight = min_child_weight
         self.max_delta_step = max_delta_step
         self.subsample = subsample
+        self.sampling_method = sampling_method
         self.colsample_bytree = colsample_bytree
         self.colsample_bylevel = colsample_bylevel
         self.colsample_bynode = colsample_bynode

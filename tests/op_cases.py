@@ -534,11 +534,23 @@ def quantize_cases():
                    rng.uniform(0, 0.19661193, n)], axis=1).astype(np.float32)
     g2[0] = (0.7310586, 0.19661193)
     g2[1] = (-0.7310586, 0.0)
+    # an all-zero gradient column with the scales the trainer derives from
+    # the column maxima: the scale of a zero maximum must stay finite
+    from xgboost_ray_amd.engine.trainer import _quant_scale
+
+    g3 = g2.copy()
+    g3[:, 0] = 0.0
+    g3[1, 0] = -0.0
+    zero_scales = [_quant_scale(float(np.abs(g3[:, j]).max()))
+                   for j in (0, 1)]
+    assert not g3[:, 0].any() and g3[:, 1].any()
     return (
         {"id": "half-even-2^30", "gpair": torch.from_numpy(gp),
          "scale_g": 1.0, "scale_h": 1.0},
         {"id": "production-scales", "gpair": torch.from_numpy(g2),
          "scale_g": SCALE_G, "scale_h": SCALE_H},
+        {"id": "zero-g-column", "gpair": torch.from_numpy(g3),
+         "scale_g": zero_scales[0], "scale_h": zero_scales[1]},
     )
 
 

@@ -306,3 +306,5 @@ def test_quantize_gpair_case(c):
     out = gpu.quantize_gpair(c["gpair"].cuda(), c["scale_g"], c["scale_h"])
     assert out.dtype == torch.int32
     _eq(out, oc.oracle_quantize(c), c["id"])
+    if c["id"] == "zero-g-column":
+        assert not out[:, 0].any()

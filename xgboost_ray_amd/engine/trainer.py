@@ -199,6 +199,13 @@ class _TreeArrays:
         self.cap = cap
 
 
+def _quant_scale(mx: float) -> float:
+    """Fixed-point scale of one gradient column: 2^30 / max|x|. An all-zero
+    column takes scale 1 (every q is 0 under any finite scale; dividing by
+    the maximum would give inf, and 0 * inf = NaN has no defined int32)."""
+    return float(2.0**_QUANT_BITS) / mx if mx > 0.0 else 1.0
+
+
 def _unpack_splits(pk):
     """Columns of a pulled ``packed`` [K, 6] int64 block (f32 gain bits,
     feature, bin, default_left, left_g, left_h) as owned arrays."""
@@ -801,8 +808,8 @@ class BoostingEngine:
             mx_d = mx.to(self.device) if self.device.type == "cuda" else mx
             self.coll.allreduce_(mx_d, op="max")
             mx = mx_d.cpu()
-        scale_g = float(2.0**_QUANT_BITS) / max(float(mx[0]), 1e-300)
-        scale_h = float(2.0**_QUANT_BITS) / max(float(mx[1]), 1e-300)
+        scale_g = _quant_scale(float(mx[0]))
+        scale_h = _quant_scale(float(mx[1]))
         self._gq_sum = None
         if gpair.is_cuda:
             # the quantize pass emits the column sums of what it writes:

@@ -384,7 +384,95 @@ def bench_walk(modes=("predict_leaf", "saabas"), n=1_000_000, F=28,
               f"{t_exact_r * 1e3:.1f} ms")
 
 
+def _spread(fn, reps=5, inner=3):
+    """(median, min, max) ms per call over ``reps`` synced windows of
+    ``inner`` calls, after one warm-up window."""
+    ts = []
+    for r in range(reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(inner):
+            fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) / inner * 1e3)
+    ts = sorted(ts[1:])
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+def bench_rank(shapes=((10_000_000, 100), (1_000_000, 1000),
+                       (6_400_000, 64)), sub_groups=2000):
+    """The HIP ranking kernels against the torch routes they replace, in one
+    process, alternating. The per-group torch loops (rank:map gradient, the
+    metrics) run on the first ``sub_groups`` groups and are reported per
+    group. The groups-of-64 shape is where both ``rank_group_stats``
+    variants can run: it measures the boundary between them."""
+    from xgboost_ray_amd.engine.metrics import get_metric
+    from xgboost_ray_amd.engine.objectives import RankMAP, RankNDCG
+
+    dev = torch.device("cuda")
+
+    def show(name, t, groups=None):
+        per = f"  {t[0] / groups * 1e3:9.3f} us/group" if groups else ""
+        print(f"  {name:34s} {t[0]:10.3f} ms  [{t[1]:.3f}, {t[2]:.3f}]{per}",
+              flush=True)
+        return t[0]
+
+    for n, glen in shapes:
+        gen = torch.Generator(device=dev).manual_seed(11)
+        margin = torch.randn(n, device=dev, generator=gen)
+        label = torch.randint(0, 5, (n,), device=dev, generator=gen).float()
+        qid = torch.arange(n, device=dev) // glen
+        G = n // glen
+        group_ptr = torch.arange(G + 1, device=dev) * glen
+        disc = ops.rank_disc_table(dev)
+        ndcg = RankNDCG()
+        print(f"rank: {n} rows in {G} groups of {glen}")
+        variants = [("auto", {})]
+        if glen <= 64:
+            variants.append(("workgroup/group", {"variant": 2}))
+        for block in (64, 128, 256):
+            variants.append((f"block {block}", {"block": block}))
+        for name, kw in variants:
+            show(f"rank_group_stats {name}", _spread(
+                lambda: ops.rank_group_stats(margin, label, group_ptr, disc,
+                                             0, max_len=glen, **kw)))
+        show("torch preparation (parent)", _spread(
+            lambda: ndcg._prep_torch(margin, label, qid)))
+        rank, stats = ops.rank_group_stats(margin, label, group_ptr, disc, 0,
+                                           max_len=glen)
+        idcg = stats[:, 2].contiguous()
+        show("lambdarank_grad (ndcg), for scale", _spread(
+            lambda: ops.gpu.lambdarank_grad(margin, label, group_ptr, rank,
+                                            idcg, True)))
+        for block in (0, 64, 128, 256):
+            show(f"lambdamap_grad block {block or 'auto'}", _spread(
+                lambda: ops.lambdamap_grad(margin, label, group_ptr,
+                                           max_len=glen, block=block)))
+        # public routes, new against RXGB_RANK_GPU=0
+        ns = sub_groups * glen
+        full = (margin, label, None, qid)
+        sub = (margin[:ns], label[:ns], None, qid[:ns].clone())
+        for route in ("hip", "torch"):
+            _os.environ["RXGB_RANK_GPU"] = "0" if route == "torch" else "1"
+            loop = sub if route == "torch" else full  # per-group torch loops
+            runs = [(RankNDCG(), "gradients", full),
+                    (RankMAP(), "gradients", loop),
+                    (get_metric("ndcg@10"), "local_stats", loop),
+                    (get_metric("map"), "local_stats", loop)]
+            for who, what, a in runs:
+                fn = getattr(who, what)
+                args = a if what == "gradients" else a + (None,)
+                quick = a is full
+                show(f"{who.name} {what} [{route}]", _spread(
+                    lambda: fn(*args), reps=5 if quick else 1,
+                    inner=3 if quick else 1), groups=len(a[0]) // glen)
+                assert who.last_route == route
+        _os.environ.pop("RXGB_RANK_GPU")
+
+
 def main():
+    if _sys.argv[1:2] == ["rank"]:
+        return bench_rank()
     if _sys.argv[1:2] == ["leaf_quantile"]:
         return bench_leaf_quantile()
     if _sys.argv[1:2] in (["predict_leaf"], ["saabas"]):

@@ -1,6 +1,7 @@
 """Ranking flagship: rank:ndcg lambdarank rounds/s on synthetic groups.
 
 Usage: python benchmarks/bench_rank.py [--rows N] [--group G] [--steps K]
+       [--eval]   (also evaluate ndcg@10 on the training set every round)
 (BASELINE configs list 'RayXGBRanker rank:ndcg on synthetic MSLR-style
 groups'; this measures the engine-level round time on one GPU.)
 """
@@ -15,7 +16,7 @@ import numpy as np
 import torch
 
 from xgboost_ray_amd.engine.quantile import BinnedMatrix
-from xgboost_ray_amd.engine.trainer import BoostingEngine
+from xgboost_ray_amd.engine.trainer import BoostingEngine, EvalPack
 
 
 def main():
@@ -25,6 +26,8 @@ def main():
     ap.add_argument("--group", type=int, default=100)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--eval", action="store_true",
+                    help="evaluate ndcg@10 on the training set each round")
     args = ap.parse_args()
     dev = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     g = torch.Generator(device=dev).manual_seed(7)
@@ -38,16 +41,23 @@ def main():
     eng = BoostingEngine(
         {"objective": "rank:ndcg", "max_depth": 8, "eta": 0.1,
          "eval_metric": ["ndcg@10"]}, dm)
-    for _ in range(args.warmup):
+    train = [EvalPack(name="train", X=None)]
+
+    def step():
         eng.update()
+        return eng.eval_sets(train) if args.eval else None
+
+    for _ in range(args.warmup):
+        step()
     torch.cuda.synchronize() if dev.type == "cuda" else None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        eng.update()
+        res = step()
     torch.cuda.synchronize() if dev.type == "cuda" else None
     dt = (time.perf_counter() - t0) / args.steps
     print(f"rank:ndcg {args.rows}x{args.features} group={args.group}: "
-          f"{dt * 1000:.2f} ms/round = {1 / dt:.1f} rounds/s")
+          f"{dt * 1000:.2f} ms/round = {1 / dt:.1f} rounds/s"
+          + (f", train {res['train']}" if args.eval else ""))
 
 
 if __name__ == "__main__":

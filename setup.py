@@ -39,7 +39,23 @@ if "--cpu-only" not in sys.argv:
                         # the hot histogram path is integer and unaffected.
                         "nvcc": ["-O3", "-std=c++17", "-ffp-contract=off"],
                     },
-                )
+                ),
+                # The ranking kernels are a module of their own: the one
+                # above keeps its build line, and so its generated code.
+                # This one opts out of packed-fp32 (v_pk_*_f32) selection;
+                # its float32 work is comparisons and one store per row.
+                cpp_extension.CUDAExtension(
+                    name="xgboost_ray_amd._hip_rank_ops",
+                    sources=[os.path.join(src_dir, "rank", "rank_ops.hip")],
+                    extra_compile_args={
+                        "cxx": ["-O3", "-std=c++17"],
+                        # -ffp-contract=off: the AP prefix sums must be the
+                        # bits of a sequential float64 cumsum
+                        "nvcc": ["-O3", "-std=c++17", "-ffp-contract=off",
+                                 "-Xclang", "-target-feature",
+                                 "-Xclang", "-packed-fp32-ops"],
+                    },
+                ),
             ]
             cmdclass = {"build_ext": cpp_extension.BuildExtension}
     except Exception as e:  # pragma: no cover

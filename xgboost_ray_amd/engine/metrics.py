@@ -12,7 +12,7 @@ from typing import Optional
 
 import torch
 
-from xgboost_ray_amd.engine.objectives import sigmoid_sizeinv
+from xgboost_ray_amd.engine.objectives import rank_hip_layout, sigmoid_sizeinv
 
 _AUC_BINS = 16384
 
@@ -232,12 +232,39 @@ class MError(Metric):
 
 
 class _PerGroupMetric(Metric):
+    """Mean of a per-group score. On the GPU the scores of all groups come
+    from one HIP launch (``ops.rank_group_stats``); the per-group torch loop
+    serves CPU tensors, groups longer than ``ops.RANK_LDS_MAX_GROUP`` and
+    RXGB_RANK_GPU=0. ``last_route`` names the one that ran."""
+
     higher_better = True
+    last_route = None
+    hip_k = 0  # truncation level handed to rank_group_stats
 
     def group_score(self, m, y) -> float:
         raise NotImplementedError
 
+    def hip_scores(self, stats) -> torch.Tensor:
+        """Per-group scores from the [G, 4] rank_group_stats sums."""
+        raise NotImplementedError
+
     def local_stats(self, margin, label, weight, qid, obj):
+        layout = rank_hip_layout(margin, qid)
+        if layout is None:
+            self.last_route = "torch"
+            return self._local_stats_torch(margin, label, weight, qid, obj)
+        from xgboost_ray_amd import ops
+
+        y = label.contiguous().float()
+        _, stats = ops.rank_group_stats(
+            margin.contiguous().float(), y, layout[0],
+            ops.rank_disc_table(margin.device), self.hip_k,
+            max_len=layout[1])
+        scores = self.hip_scores(stats)
+        self.last_route = "hip"
+        return torch.stack([scores.sum(), scores.new_tensor(len(scores))])
+
+    def _local_stats_torch(self, margin, label, weight, qid, obj):
         if qid is None:
             qid = torch.zeros(len(label), dtype=torch.int64, device=margin.device)
         total = torch.zeros(2, dtype=torch.float64, device=margin.device)
@@ -259,8 +286,13 @@ class NDCG(_PerGroupMetric):
 
     def __init__(self, k: Optional[int] = None):
         self.k = k
+        self.hip_k = k or 0
         if k:
             self.name = f"ndcg@{k}"
+
+    def hip_scores(self, stats):
+        dcg, idcg = stats[:, 0], stats[:, 1]
+        return torch.where(idcg > 0, dcg / idcg, torch.ones_like(dcg))
 
     def group_score(self, m, y):
         n = len(y)
@@ -278,6 +310,11 @@ class NDCG(_PerGroupMetric):
 
 class MAP(_PerGroupMetric):
     name = "map"
+
+    def hip_scores(self, stats):
+        # ap >= 1 / L with a relevant row, and exactly 0 without one
+        ap = stats[:, 3]
+        return torch.where(ap > 0, ap, torch.ones_like(ap))
 
     def group_score(self, m, y):
         order = torch.argsort(m.double(), descending=True, stable=True)

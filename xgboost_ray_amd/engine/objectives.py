@@ -262,6 +262,44 @@ class SoftProb(SoftmaxBase):
         return torch.softmax(margin, dim=1)
 
 
+def rank_group_layout(qid, device):
+    """(group_ptr int64 [G+1] on ``device``, longest group) of a sorted qid
+    vector. Cached on the qid tensor object itself, keyed on its
+    ``_version``: the objective and every metric object (the trainer makes
+    new ones each round) share it, so the boundary search and its sync
+    happen once per data set, not once per round. That holds for a caller
+    that passes the SAME tensor object each time, as the trainer does with
+    ``dtrain.qid``; one that slices, copies or ``.to()``s qid per call gets
+    a new object and pays the search and its two syncs on every call."""
+    hit = getattr(qid, "_rxgb_rank_layout", None)
+    if hit is not None and hit[:2] == (qid._version, device):
+        return hit[2], hit[3]
+    q = qid.to(device)
+    n = q.shape[0]
+    change = torch.ones(n, dtype=torch.bool, device=device)
+    change[1:] = q[1:] != q[:-1]
+    starts = torch.nonzero(change).flatten()
+    group_ptr = torch.cat([starts, starts.new_tensor([n])])
+    max_len = int((group_ptr[1:] - group_ptr[:-1]).max())
+    qid._rxgb_rank_layout = (qid._version, device, group_ptr, max_len)
+    return group_ptr, max_len
+
+
+def rank_hip_layout(margin, qid):
+    """``rank_group_layout`` when the HIP ranking kernels serve this call,
+    else None: they need a float vector on the GPU, every group within
+    RANK_LDS_MAX_GROUP rows, and RXGB_RANK_GPU not set to 0."""
+    from xgboost_ray_amd import ops
+
+    if (not margin.is_cuda or margin.dim() != 1 or qid is None
+            or margin.numel() == 0 or not ops.rank_gpu_enabled()):
+        return None
+    group_ptr, max_len = rank_group_layout(qid, margin.device)
+    if max_len > ops.RANK_LDS_MAX_GROUP:
+        return None
+    return group_ptr, max_len
+
+
 class LambdaRankBase(Objective):
     """Pairwise LambdaRank objectives over qid groups.
 
@@ -366,11 +404,15 @@ class LambdaRankBase(Objective):
                 delta = torch.abs(dg * dd) / idcg
                 lam = lam * delta
                 hess = hess * delta
-            lam = torch.where(pos, lam, torch.zeros_like(lam)).to(g.dtype)
-            hess = torch.where(pos, hess, torch.zeros_like(hess)).to(g.dtype)
+            # on the GPU (rank:map groups too long for the HIP kernel) the
+            # per-row sums stay float64 as in the kernels, so both GPU
+            # routes meet one bound; the CPU path is float32 as before
+            acc = torch.float64 if device.type == "cuda" else g.dtype
+            lam = torch.where(pos, lam, torch.zeros_like(lam)).to(acc)
+            hess = torch.where(pos, hess, torch.zeros_like(hess)).to(acc)
             # pair (i, j): i should rank above j -> push m_i up, m_j down
-            g[s:e] += -lam.sum(dim=1) + lam.sum(dim=0)
-            h[s:e] += hess.sum(dim=1) + hess.sum(dim=0)
+            g[s:e] += (-lam.sum(dim=1) + lam.sum(dim=0)).to(g.dtype)
+            h[s:e] += (hess.sum(dim=1) + hess.sum(dim=0)).to(g.dtype)
         return self._apply_weight(g, h, weight)
 
     def _gradients_gpu(self, margin, label, weight, qid):
@@ -378,6 +420,23 @@ class LambdaRankBase(Objective):
         per-doc accumulation (no atomics)."""
         from xgboost_ray_amd.ops import gpu as gpu_ops
 
+        group_ptr, rank, idcg = self._prep_torch(margin, label, qid)
+        gpair = gpu_ops.lambdarank_grad(
+            margin.contiguous().float(),
+            label.contiguous().float(),
+            group_ptr,
+            rank,
+            idcg,
+            self.ndcg_weighting,
+        )
+        if weight is not None:
+            gpair = gpair * weight.unsqueeze(1)
+        return gpair
+
+    def _prep_torch(self, margin, label, qid):
+        """(group_ptr, rank, idcg) for ``lambdarank_grad`` from torch ops:
+        the group structure, and for rank:ndcg four global stable argsorts
+        and a scatter-add (kept callable on its own for the benchmark)."""
         device = margin.device
         qid = qid.to(device)
         n = margin.shape[0]
@@ -412,33 +471,35 @@ class LambdaRankBase(Objective):
         else:
             rank = torch.zeros(n, dtype=torch.int32, device=device)
             idcg = torch.zeros(1, dtype=torch.float64, device=device)
-
-        gpair = gpu_ops.lambdarank_grad(
-            margin.contiguous().float(),
-            label.contiguous().float(),
-            group_ptr,
-            rank,
-            idcg,
-            self.ndcg_weighting,
-        )
-        if weight is not None:
-            gpair = gpair * weight.unsqueeze(1)
-        return gpair
+        return group_ptr, rank, idcg
 
 
 class RankMAP(LambdaRankBase):
     """rank:map - pairwise lambdas weighted by |delta-AP| (binary
-    relevance). Uses the generic per-group path on every device (no
-    dedicated HIP kernel; MAP weighting is a rarely-hot objective)."""
+    relevance). On the GPU one HIP kernel (``ops.lambdamap_grad``) sorts
+    every group and runs its pair loop; the generic per-group loop serves
+    CPU tensors, groups longer than ``ops.RANK_LDS_MAX_GROUP`` and
+    RXGB_RANK_GPU=0. ``last_route`` names the one that ran."""
 
     name = "rank:map"
     default_metric = "map"
     map_weighting = True
+    last_route = None
 
     def _gradients_gpu(self, margin, label, weight, qid):
-        # no dedicated HIP kernel: run the generic group loop on the
-        # device tensors (correct, just not the fast path)
-        return self._gradients_generic(margin, label, weight, qid)
+        layout = rank_hip_layout(margin, qid)
+        if layout is None:
+            self.last_route = "torch"
+            return self._gradients_generic(margin, label, weight, qid)
+        from xgboost_ray_amd import ops
+
+        gpair = ops.lambdamap_grad(
+            margin.contiguous().float(), label.contiguous().float(),
+            layout[0], max_len=layout[1])
+        self.last_route = "hip"
+        if weight is not None:
+            gpair = gpair * weight.unsqueeze(1)
+        return gpair
 
 
 class RankPairwise(LambdaRankBase):
@@ -447,9 +508,37 @@ class RankPairwise(LambdaRankBase):
 
 
 class RankNDCG(LambdaRankBase):
+    """rank:ndcg. On the GPU the ranks and the ideal DCG of every group
+    come from one HIP launch (``ops.rank_group_stats``) over a cached group
+    layout; the torch preparation of ``LambdaRankBase`` serves groups
+    longer than ``ops.RANK_LDS_MAX_GROUP`` and RXGB_RANK_GPU=0.
+    ``last_route`` names the one that ran."""
+
     name = "rank:ndcg"
     ndcg_weighting = True
     default_metric = "ndcg"
+    last_route = None
+
+    def _gradients_gpu(self, margin, label, weight, qid):
+        layout = rank_hip_layout(margin, qid)
+        if layout is None:
+            self.last_route = "torch"
+            return super()._gradients_gpu(margin, label, weight, qid)
+        from xgboost_ray_amd import ops
+        from xgboost_ray_amd.ops import gpu as gpu_ops
+
+        group_ptr, max_len = layout
+        m = margin.contiguous().float()
+        y = label.contiguous().float()
+        rank, stats = ops.rank_group_stats(
+            m, y, group_ptr, ops.rank_disc_table(m.device), 0,
+            max_len=max_len)
+        gpair = gpu_ops.lambdarank_grad(
+            m, y, group_ptr, rank, stats[:, 2].contiguous(), True)
+        self.last_route = "hip"
+        if weight is not None:
+            gpair = gpair * weight.unsqueeze(1)
+        return gpair
 
 
 class CustomObjective(Objective):

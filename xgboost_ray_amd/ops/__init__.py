@@ -460,6 +460,65 @@ def mvs_sample(gpair, c, S, M, key):
     return _impl(gpair).mvs_sample(gpair, c, S, M, key)
 
 
+RANK_LDS_MAX_GROUP = _cpu.RANK_LDS_MAX_GROUP
+
+
+def rank_gpu_enabled():
+    """RXGB_RANK_GPU=0 keeps the ranking objectives and metrics on their
+    torch routes (the HIP ranking kernels are on by default)."""
+    import os
+
+    return os.environ.get("RXGB_RANK_GPU") != "0"
+
+
+def rank_disc_table(device):
+    """float64 [RANK_LDS_MAX_GROUP] DCG discounts 1 / log2(r + 2) on
+    ``device``: computed on the host with numpy, uploaded once and cached,
+    so no device log2 enters a DCG."""
+    if torch.device(device).type == "cuda":
+        return _gpu().rank_disc_table(device)
+    return torch.from_numpy(_cpu.rank_disc_table())
+
+
+def rank_group_stats(margin, label, group_ptr, disc, k, max_len=None, **kw):
+    """Stable descending rank of every row inside its query group, and the
+    DCG / AP sums of every group.
+
+    margin, label: f32 [n]; group_ptr: int64 [G+1] row offsets of the
+    groups (rows of a group are contiguous); disc: ``rank_disc_table``;
+    k: truncation level, 0 = whole group. No group may be longer than
+    RANK_LDS_MAX_GROUP; ``max_len``, the longest group, saves the GPU route
+    a sync when the caller knows it.
+    Returns (rank i32 [n], stats f64 [G, 4]). rank orders by descending
+    margin, ties (-0.0 == +0.0 included) in row order. With
+    gain = 2^label - 1 in float64, stats[g] = [dcg@k, idcg@k, idcg, ap]:
+    dcg@k sums gain * disc[rank] over ranks < min(k, L); idcg@k and idcg
+    are the same sums over the gains sorted descending; ap is the average
+    over relevant rows (label > 0) of (relevant rows at ranks <= p) /
+    (p + 1), 0 without a relevant row. On the GPU every sum has a fixed
+    order, so equal inputs give equal bytes.
+    """
+    return _impl(margin).rank_group_stats(
+        margin, label, group_ptr, disc, k, max_len, **kw)
+
+
+def lambdamap_grad(margin, label, group_ptr, max_len=None, **kw):
+    """rank:map gradient pairs f32 [n, 2] (unweighted).
+
+    With rank, rel = label > 0, R = #rel, prefix[p] = #rel at ranks <= p,
+    t[p] = prefix[p] / (p + 1) and S[p] = sum_{q <= p} rel_q / (q + 1) per
+    group as in ``rank_group_stats``: every ordered pair with
+    label_i > label_j has rho = 1 / (1 + exp(m_i - m_j)) (difference in
+    float32, the rest float64), delta = |t[hi] - t[lo] - (S[hi-1] - S[lo])|
+    / R at lo / hi = the smaller / larger of the two ranks, and adds
+    -rho * delta to g_i, +rho * delta to g_j and
+    max(rho (1 - rho), 1e-16) * delta to both hessians. Groups with R = 0
+    or fewer than two rows give zeros.
+    """
+    return _impl(margin).lambdamap_grad(margin, label, group_ptr, max_len,
+                                        **kw)
+
+
 def grad_fused(margin, label, weight, scale_pos_weight, mode):
     """Fused objective gradient + |g|/|h| max for the hot objectives
     (mode 0 = reg:squarederror, 1 = binary:logistic). GPU only: returns

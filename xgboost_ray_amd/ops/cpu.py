@@ -843,3 +843,90 @@ def tree_shap_interactions(X, paths, out, max_out_bytes=None):
                     outn[:, int(feat[c]), int(feat[j])] += np.where(
                         dead, 0.0, half * s * (o[j] - z[j]) * v)
     return out
+
+
+# ---------------------------------------------------------------------------
+# Ranking: per-group stable descending ranks, DCG / AP sums and the rank:map
+# lambdas (contract: docs/parity.md "Ranking on the device"). Plain numpy,
+# one group at a time - the twins of the HIP kernels, not a fast path.
+# ---------------------------------------------------------------------------
+# longest query group the HIP kernels sort in LDS
+RANK_LDS_MAX_GROUP = 2048
+
+
+def rank_disc_table(length=RANK_LDS_MAX_GROUP):
+    """float64 [length] DCG discounts, disc[r] = 1 / log2(r + 2)."""
+    import numpy as np
+
+    return 1.0 / np.log2(np.arange(length, dtype=np.float64) + 2.0)
+
+
+def _rank_order(m):
+    """Stable descending order of float32 margins; -0.0 ties with +0.0."""
+    import numpy as np
+
+    return np.argsort(-m.astype(np.float64), kind="stable")
+
+
+def rank_group_stats(margin, label, group_ptr, disc, k, max_len=None):
+    import numpy as np
+
+    m = np.asarray(_as_numpy(margin), np.float32)
+    y = np.asarray(_as_numpy(label), np.float32)
+    gp = np.asarray(_as_numpy(group_ptr), np.int64)
+    disc = np.asarray(_as_numpy(disc), np.float64)
+    G = len(gp) - 1
+    rank = np.zeros(len(m), np.int32)
+    stats = np.zeros((G, 4), np.float64)
+    for g in range(G):
+        s, e = int(gp[g]), int(gp[g + 1])
+        L = e - s
+        if L == 0:
+            continue
+        kk = L if k <= 0 or k > L else int(k)
+        order = _rank_order(m[s:e])
+        rank[s + order] = np.arange(L, dtype=np.int32)
+        gain = np.exp2(y[s:e].astype(np.float64)) - 1.0
+        d = disc[:L]
+        ideal = np.sort(gain)[::-1] * d
+        rel = (y[s:e][order] > 0).astype(np.float64)
+        R = rel.sum()
+        ap = (np.cumsum(rel) / np.arange(1, L + 1) * rel).sum()
+        stats[g] = ((gain[order] * d)[:kk].sum(), ideal[:kk].sum(),
+                    ideal.sum(), ap / R if R > 0 else 0.0)
+    return torch.from_numpy(rank), torch.from_numpy(stats)
+
+
+def lambdamap_grad(margin, label, group_ptr, max_len=None):
+    import numpy as np
+
+    m32 = np.asarray(_as_numpy(margin), np.float32)
+    y32 = np.asarray(_as_numpy(label), np.float32)
+    gp = np.asarray(_as_numpy(group_ptr), np.int64)
+    out = np.zeros((len(m32), 2), np.float64)
+    for g in range(len(gp) - 1):
+        s, e = int(gp[g]), int(gp[g + 1])
+        L = e - s
+        m, y = m32[s:e], y32[s:e]
+        win = y[:, None] > y[None, :]
+        order = _rank_order(m)
+        rel = (y[order] > 0).astype(np.float64)
+        R = rel.sum()
+        if L < 2 or R == 0 or not win.any():
+            continue
+        rank = np.empty(L, np.int64)
+        rank[order] = np.arange(L)
+        pos = np.arange(1, L + 1, dtype=np.float64)
+        t = np.cumsum(rel) / pos
+        S = np.cumsum(rel / pos)
+        lo = np.minimum(rank[:, None], rank[None, :])
+        hi = np.maximum(rank[:, None], rank[None, :])
+        delta = np.abs(t[hi] - t[lo] - (S[np.maximum(hi - 1, 0)] - S[lo])) / R
+        with np.errstate(over="ignore"):
+            rho = 1.0 / (1.0 + np.exp((m[:, None] - m[None, :]).astype(
+                np.float64)))
+        lam = np.where(win, rho * delta, 0.0)
+        hess = np.where(win, np.maximum(rho * (1.0 - rho), 1e-16) * delta, 0.0)
+        out[s:e, 0] = -lam.sum(1) + lam.sum(0)
+        out[s:e, 1] = hess.sum(1) + hess.sum(0)
+    return torch.from_numpy(out.astype(np.float32))

@@ -303,6 +303,59 @@ def lambdarank_grad(margin, label, group_ptr, rank, idcg, use_ndcg):
     )
 
 
+RANK_LDS_MAX_GROUP = 2048  # checked against the extension's own constant
+_rank_disc = {}
+_rank_ext = None
+
+
+def _load_rank():
+    """The ranking kernels' module (csrc/rank); required like ``_hip_ops``."""
+    global _rank_ext
+    if _rank_ext is None:
+        _load()  # same build; raises the build hint if nothing is built
+        import importlib
+
+        _rank_ext = importlib.import_module("xgboost_ray_amd._hip_rank_ops")
+        assert _rank_ext.RANK_LDS_MAX_GROUP == RANK_LDS_MAX_GROUP
+    return _rank_ext
+
+
+def rank_disc_table(device):
+    """The float64 discount table 1 / log2(r + 2), r < RANK_LDS_MAX_GROUP:
+    made once with numpy and uploaded once per device."""
+    dev = torch.device(device)
+    if dev not in _rank_disc:
+        from xgboost_ray_amd.ops.cpu import rank_disc_table as host_table
+
+        _rank_disc[dev] = torch.from_numpy(
+            host_table(RANK_LDS_MAX_GROUP)).to(dev)
+    return _rank_disc[dev]
+
+
+def _rank_max_len(group_ptr, max_len):
+    if max_len is None:  # one sync; callers that loop pass it in
+        d = group_ptr[1:] - group_ptr[:-1]
+        max_len = int(d.max()) if d.numel() else 0
+    return int(max_len)
+
+
+def rank_group_stats(margin, label, group_ptr, disc, k, max_len=None,
+                     variant=0, block=0):
+    """variant: 0 picks by the longest group (<= 64 rows: a wave per
+    group, else a workgroup per group), 1 / 2 force one; block: workgroup
+    size override. Both exist for the benchmark's sweep."""
+    rank, stats = _load_rank().rank_group_stats(
+        margin, label, group_ptr, disc, int(k or 0),
+        _rank_max_len(group_ptr, max_len), int(variant), int(block))
+    return rank, stats
+
+
+def lambdamap_grad(margin, label, group_ptr, max_len=None, block=0):
+    return _load_rank().lambdamap_grad(
+        margin, label, group_ptr, _rank_max_len(group_ptr, max_len),
+        int(block))
+
+
 def update_margins(margin, ridx, starts, counts, leaf_values,
                    ridx_b=None, parity=None):
     # starts/counts/leaf_values stay on the HOST: the extension stages

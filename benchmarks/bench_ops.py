@@ -399,6 +399,22 @@ def _spread(fn, reps=5, inner=3):
     return ts[len(ts) // 2], ts[0], ts[-1]
 
 
+def _spread_alt(fns, reps=5, inner=3):
+    """``_spread`` of several routes whose windows alternate, so that a
+    drift of the clocks falls on all of them alike."""
+    ts = [[] for _ in fns]
+    for r in range(reps + 1):
+        for t, fn in zip(ts, fns):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(inner):
+                fn()
+            torch.cuda.synchronize()
+            t.append((time.perf_counter() - t0) / inner * 1e3)
+    ts = [sorted(t[1:]) for t in ts]
+    return [(t[len(t) // 2], t[0], t[-1]) for t in ts]
+
+
 def bench_rank(shapes=((10_000_000, 100), (1_000_000, 1000),
                        (6_400_000, 64)), sub_groups=2000):
     """The HIP ranking kernels against the torch routes they replace, in one
@@ -444,6 +460,39 @@ def bench_rank(shapes=((10_000_000, 100), (1_000_000, 1000),
         show("lambdarank_grad (ndcg), for scale", _spread(
             lambda: ops.gpu.lambdarank_grad(margin, label, group_ptr, rank,
                                             idcg, True)))
+        # top-k pair truncation against the all-pairs route it shortens,
+        # windows alternating; k = glen is the all-pairs gradient on the
+        # new kernel
+        def all_ndcg():
+            r, s = ops.rank_group_stats(margin, label, group_ptr, disc, 0,
+                                        max_len=glen)
+            return ops.gpu.lambdarank_grad(margin, label, group_ptr, r,
+                                           s[:, 2].contiguous(), True)
+
+        def topk(k, nd, **kw):
+            return lambda: ops.lambdarank_topk_grad(
+                margin, label, group_ptr, disc, k, nd, max_len=glen, **kw)
+
+        rows = [("rank_group_stats + lambdarank_grad", all_ndcg),
+                ("lambdarank_grad (pairwise)",
+                 lambda: ops.gpu.lambdarank_grad(margin, label, group_ptr,
+                                                 rank, idcg, False))]
+        for k in (8, 32, glen):
+            for nd in (True, False):
+                tag = f"k={k} {'ndcg' if nd else 'pairwise'}"
+                rows.append((f"lambdarank_topk_grad {tag}", topk(k, nd)))
+                if glen <= 64:  # both variants can run: their boundary
+                    rows.append((f"  workgroup/group {tag}",
+                                 topk(k, nd, variant=2)))
+                    rows.append((f"  wave/group {tag}",
+                                 topk(k, nd, variant=1)))
+                    assert torch.allclose(rows[-1][1](), rows[-2][1](),
+                                          rtol=1e-6, atol=1e-12)
+        for (name, _), t in zip(rows, _spread_alt([f for _, f in rows])):
+            show(name, t)
+        for block in (64, 128, 256):
+            show(f"lambdarank_topk_grad k=32 ndcg block {block}", _spread(
+                topk(32, True, block=block)))
         for block in (0, 64, 128, 256):
             show(f"lambdamap_grad block {block or 'auto'}", _spread(
                 lambda: ops.lambdamap_grad(margin, label, group_ptr,

@@ -2,6 +2,7 @@
 
 Usage: python benchmarks/bench_rank.py [--rows N] [--group G] [--steps K]
        [--eval]   (also evaluate ndcg@10 on the training set every round)
+       [--topk K] (lambdarank_pair_method="topk" with K pairs per sample)
 (BASELINE configs list 'RayXGBRanker rank:ndcg on synthetic MSLR-style
 groups'; this measures the engine-level round time on one GPU.)
 """
@@ -28,6 +29,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--eval", action="store_true",
                     help="evaluate ndcg@10 on the training set each round")
+    ap.add_argument("--topk", type=int, default=0,
+                    help="top-k pair truncation with this k (0: all pairs)")
     args = ap.parse_args()
     dev = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     g = torch.Generator(device=dev).manual_seed(7)
@@ -38,9 +41,12 @@ def main():
     qid = torch.arange(args.rows, device=dev) // args.group
     dm = BinnedMatrix.build(X, label=y, qid=qid, max_bin=256)
     del X
-    eng = BoostingEngine(
-        {"objective": "rank:ndcg", "max_depth": 8, "eta": 0.1,
-         "eval_metric": ["ndcg@10"]}, dm)
+    params = {"objective": "rank:ndcg", "max_depth": 8, "eta": 0.1,
+              "eval_metric": ["ndcg@10"]}
+    if args.topk:
+        params.update(lambdarank_pair_method="topk",
+                      lambdarank_num_pair_per_sample=args.topk)
+    eng = BoostingEngine(params, dm)
     train = [EvalPack(name="train", X=None)]
 
     def step():
@@ -55,7 +61,8 @@ def main():
         res = step()
     torch.cuda.synchronize() if dev.type == "cuda" else None
     dt = (time.perf_counter() - t0) / args.steps
-    print(f"rank:ndcg {args.rows}x{args.features} group={args.group}: "
+    print(f"rank:ndcg {args.rows}x{args.features} group={args.group} "
+          f"pairs={'top-%d' % args.topk if args.topk else 'all'}: "
           f"{dt * 1000:.2f} ms/round = {1 / dt:.1f} rounds/s"
           + (f", train {res['train']}" if args.eval else ""))
 

@@ -1,5 +1,6 @@
 // Ranking kernels for AMD Instinct MI355X (CDNA4, gfx950): the in-LDS group
-// sort, ranks + DCG / AP sums, and the rank:map pair loop. Built as its own
+// sort, ranks + DCG / AP sums, the rank:map pair loop and the LambdaRank
+// pair loop with top-k truncation. Built as its own
 // extension module (xgboost_ray_amd._hip_rank_ops), so that adding it leaves
 // the build line and the generated code of csrc/kernels.hip as they were.
 
@@ -366,6 +367,187 @@ __global__ __launch_bounds__(RANK_MAX_THREADS) void lambdamap_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// LambdaRank with top-k pair truncation (rank:pairwise / rank:ndcg,
+// lambdarank_pair_method="topk"): a pair (i, j) with label_i > label_j
+// counts iff min(rank_i, rank_j) < k. One launch sorts every group, forms
+// idcg and runs the pair loop; the loop works in RANK space, so the
+// truncation is a loop bound and not a test per pair.
+//
+// One pair term of row p against partner q (both in rank order). The row
+// collects -rho w when it wins the pair and +rho w when it loses it.
+template <bool NDCG>
+__device__ __forceinline__ void topk_pair(float mp, float yp, double gp,
+                                          double dp, float mq, float yq,
+                                          double gq, double dq, double inv,
+                                          double& g, double& h) {
+  if (yq == yp) return;
+  const bool win = yp > yq;
+  const double rho = 1.0 / (1.0 + exp((double)(win ? mp - mq : mq - mp)));
+  double hij = rho * (1.0 - rho);
+  if (hij < 1e-16) hij = 1e-16;
+  if (NDCG) {
+    const double w = fabs((gp - gq) * (dp - dq)) * inv;
+    g += win ? -(rho * w) : rho * w;
+    h += hij * w;
+  } else {
+    g += win ? -rho : rho;
+    h += hij;
+  }
+}
+
+// Workgroup per group (L <= RANK_LDS_MAX_GROUP). Dynamic LDS per element of
+// the launch's largest padded group Pmax, all of it indexed by rank p once
+// the sort is done:
+//   u64 sort key [Pmax]   8 B  low word = row index inside the group (kept),
+//                              high word rewritten in place to the margin
+//                              f32: okey is invertible, so the sorted key
+//                              IS the rank-ordered margin (-0.0 comes back
+//                              as +0.0; every difference keeps its value)
+//   f32 label, row order  4 B  dead after the gather; then the wave sums
+//   u32 label key [Pmax]  4 B  sorted with the margins for idcg; element p
+//                              is read, then overwritten by label-at-rank-p
+//   f64 gain, f64 disc   16 B  ndcg only, one exp2 per element
+// = 32 B (ndcg: 64 KiB at P = 2048, two workgroups per 160 KiB CU) or 16 B
+// (pairwise: 32 KiB, five per CU by LDS). No static LDS, so the largest
+// launch is exactly 64 KiB.
+// Pair loop, LDS reads only, kk = min(k, L):
+//   head rows p < kk have L - 1 partners: one WAVE per row, lane l takes
+//     q = l, l + 64, ... ascending; xor butterfly; lane 0 stores.
+//   tail rows p >= kk have kk partners: one THREAD per row, q = 0 .. kk-1
+//     ascending (every lane reads the same q: an LDS broadcast).
+// Both halves cost about kk * L / 64 wave steps. Sums are float64 in that
+// fixed order, one float32 store per row, no atomics.
+template <bool NDCG>
+__global__ __launch_bounds__(RANK_MAX_THREADS) void lambdarank_topk_kernel(
+    const float* __restrict__ margin, const float* __restrict__ label,
+    const int64_t* __restrict__ group_ptr, const double* __restrict__ disc,
+    float2* __restrict__ out, int64_t n, int k, int Pmax) {
+  extern __shared__ unsigned long long rank_smem[];
+  unsigned long long* skey = rank_smem;
+  const uint32_t* sidx = (const uint32_t*)rank_smem;  // word 2p, after sort
+  float* smar = (float*)rank_smem;                    // word 2p + 1
+  float* slab = (float*)(skey + Pmax);
+  uint32_t* lkey = (uint32_t*)(slab + Pmax);
+  float* sy = (float*)lkey;
+  double* sgain = (double*)(lkey + Pmax);
+  double* sdisc = sgain + Pmax;
+  double* sred = (double*)slab;  // Pmax >= 64 floats: room for every wave
+  const int g = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+  const int lane = tid & (WAVE - 1), wv = tid / WAVE, nw = T / WAVE;
+  const int64_t s0 = group_ptr[g], s1 = group_ptr[g + 1];
+  if (!rank_group_ok(s0, s1, n, Pmax)) return;  // block-uniform
+  const int L = (int)(s1 - s0);
+  if (L < 2) return;  // `out` starts zeroed
+  const int P = rank_pad(L);
+  for (int e = tid; e < P; e += T) {
+    const bool live = e < L;
+    const float y = live ? label[s0 + e] : 0.f;
+    skey[e] = live ? rank_key(margin[s0 + e], e) : ~0ull;
+    slab[e] = y;
+    if (NDCG) lkey[e] = live ? ~rank_okey(y) : ~0u;
+  }
+  __syncthreads();
+  bitonic_block_sort<unsigned long long, uint32_t, NDCG>(skey, lkey, P);
+  double part = 0.0;
+  for (int p = tid; p < L; p += T) {
+    const unsigned long long key = skey[p];
+    const float y = slab[(uint32_t)key];  // < L: pads sort last
+    if (NDCG) {
+      const double d = disc[p];
+      part += (exp2((double)rank_okey_inv(~lkey[p])) - 1.0) * d;
+      sgain[p] = exp2((double)y) - 1.0;
+      sdisc[p] = d;
+    }
+    smar[2 * p + 1] = rank_okey_inv(~(uint32_t)(key >> 32));
+    sy[p] = y;
+  }
+  __syncthreads();  // rank-ordered arrays complete, slab dead
+  double inv = 1.0;
+  if (NDCG) {
+    part = wave_sum_f64(part);
+    if (lane == 0) sred[wv] = part;
+    __syncthreads();
+    double idcg = sred[0];
+    for (int w = 1; w < nw; ++w) idcg += sred[w];
+    if (!(idcg > 0.0)) return;  // block-uniform; zeros stay
+    inv = 1.0 / idcg;
+  }
+  const int kk = min(k, L);
+  for (int p = wv; p < kk; p += nw) {  // head rows: wave-uniform
+    const float mp = smar[2 * p + 1], yp = sy[p];
+    const double gp = NDCG ? sgain[p] : 0.0, dp = NDCG ? sdisc[p] : 0.0;
+    double gacc = 0.0, hacc = 0.0;
+    for (int q = lane; q < L; q += WAVE)
+      topk_pair<NDCG>(mp, yp, gp, dp, smar[2 * q + 1], sy[q],
+                      NDCG ? sgain[q] : 0.0, NDCG ? sdisc[q] : 0.0, inv, gacc,
+                      hacc);
+    gacc = wave_sum_f64(gacc);
+    hacc = wave_sum_f64(hacc);
+    if (lane == 0)
+      out[s0 + sidx[2 * p]] = make_float2((float)gacc, (float)hacc);
+  }
+  for (int p = kk + tid; p < L; p += T) {  // tail rows
+    const float mp = smar[2 * p + 1], yp = sy[p];
+    const double gp = NDCG ? sgain[p] : 0.0, dp = NDCG ? sdisc[p] : 0.0;
+    double gacc = 0.0, hacc = 0.0;
+    for (int q = 0; q < kk; ++q)
+      topk_pair<NDCG>(mp, yp, gp, dp, smar[2 * q + 1], sy[q],
+                      NDCG ? sgain[q] : 0.0, NDCG ? sdisc[q] : 0.0, inv, gacc,
+                      hacc);
+    out[s0 + sidx[2 * p]] = make_float2((float)gacc, (float)hacc);
+  }
+}
+
+// Wave per group (L <= 64), four groups per 256-thread workgroup: sort,
+// idcg and the rank-ordered values stay in registers; a partner's values
+// come from lane q by __shfl with a wave-uniform q. Lane p walks
+// q = 0 .. L-1 ascending and takes the pairs with p < kk or q < kk.
+template <bool NDCG>
+__global__ __launch_bounds__(RANK_MAX_THREADS)
+void lambdarank_topk_wave_kernel(
+    const float* __restrict__ margin, const float* __restrict__ label,
+    const int64_t* __restrict__ group_ptr, const double* __restrict__ disc,
+    float2* __restrict__ out, int G, int64_t n, int k) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int g = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
+  if (g >= G) return;  // wave-uniform
+  const int64_t s0 = group_ptr[g], s1 = group_ptr[g + 1];
+  if (!rank_group_ok(s0, s1, n, WAVE)) return;
+  const int L = (int)(s1 - s0);
+  if (L < 2) return;
+  const bool live = lane < L;
+  const float m = live ? margin[s0 + lane] : 0.f;
+  const float y = live ? label[s0 + lane] : 0.f;
+  unsigned long long key = live ? rank_key(m, lane) : ~0ull;
+  key = bitonic_wave_sort(key, lane);
+  // lane p now holds rank p
+  const int idx = (int)(uint32_t)key & (WAVE - 1);
+  const float mr = rank_okey_inv(~(uint32_t)(key >> 32));
+  const float yr = __shfl(y, idx);
+  double gain = 0.0, d = 0.0, inv = 1.0;
+  if (NDCG) {
+    uint32_t lkey = live ? ~rank_okey(y) : ~0u;
+    lkey = bitonic_wave_sort(lkey, lane);
+    d = live ? disc[lane] : 0.0;
+    gain = exp2((double)yr) - 1.0;
+    const double idcg = wave_sum_f64(
+        live ? (exp2((double)rank_okey_inv(~lkey)) - 1.0) * d : 0.0);
+    if (!(idcg > 0.0)) return;  // wave-uniform
+    inv = 1.0 / idcg;
+  }
+  const int kk = min(k, L);
+  double gacc = 0.0, hacc = 0.0;
+  for (int q = 0; q < L; ++q) {
+    const float mq = __shfl(mr, q), yq = __shfl(yr, q);
+    const double gq = NDCG ? __shfl(gain, q) : 0.0;
+    const double dq = NDCG ? __shfl(d, q) : 0.0;
+    if (live && (lane < kk || q < kk))
+      topk_pair<NDCG>(mr, yr, gain, d, mq, yq, gq, dq, inv, gacc, hacc);
+  }
+  if (live) out[s0 + idx] = make_float2((float)gacc, (float)hacc);
+}
+
 static int rank_pad_host(int64_t len) {
   int P = WAVE;
   while (P < len) P <<= 1;
@@ -482,7 +664,83 @@ torch::Tensor lambdamap_grad(torch::Tensor margin, torch::Tensor label,
   return out;
 }
 
+template <bool NDCG>
+static void launch_lambdarank_topk(const torch::Tensor& margin,
+                                   const torch::Tensor& label,
+                                   const torch::Tensor& group_ptr,
+                                   const torch::Tensor& disc,
+                                   torch::Tensor& out, int k, int64_t max_len,
+                                   int64_t block, bool wave) {
+  const int64_t n = margin.numel();
+  const int64_t G = group_ptr.numel() - 1;
+  auto stream = c10::hip::getCurrentHIPStream();
+  if (wave) {
+    const int T = rank_threads(block, RANK_MAX_THREADS);
+    hipLaunchKernelGGL(lambdarank_topk_wave_kernel<NDCG>,
+                       dim3((uint32_t)ceil_div(G, T / WAVE)), dim3(T), 0,
+                       stream.stream(), margin.data_ptr<float>(),
+                       label.data_ptr<float>(),
+                       group_ptr.data_ptr<int64_t>(), disc.data_ptr<double>(),
+                       (float2*)out.data_ptr<float>(), (int)G, n, k);
+  } else {
+    const int Pmax = rank_pad_host(max_len);
+    const int T = rank_block_threads(Pmax, block);
+    hipLaunchKernelGGL(lambdarank_topk_kernel<NDCG>, dim3((uint32_t)G),
+                       dim3(T), (size_t)Pmax * (NDCG ? 32 : 16),
+                       stream.stream(), margin.data_ptr<float>(),
+                       label.data_ptr<float>(),
+                       group_ptr.data_ptr<int64_t>(), disc.data_ptr<double>(),
+                       (float2*)out.data_ptr<float>(), n, k, Pmax);
+  }
+  CHECK_HIP(hipGetLastError());
+}
+
+// rank:pairwise / rank:ndcg gradient pairs f32 [n, 2] over the pairs with
+// min(rank_i, rank_j) < k; max_len / block as above; variant: 1 forces
+// wave-per-group (max_len <= 64), 2 workgroup-per-group, 0 picks: the wave
+// kernel always walks all L partners, so it wins only from about k = 32 on
+// (measured: docs/parity.md) and serves max_len <= 64 with k >= 32.
+torch::Tensor lambdarank_topk_grad(torch::Tensor margin, torch::Tensor label,
+                                   torch::Tensor group_ptr,
+                                   torch::Tensor disc, int64_t k, bool ndcg,
+                                   int64_t max_len, int64_t block,
+                                   int64_t variant) {
+  rank_check_inputs("lambdarank_topk_grad", margin, label, group_ptr,
+                    max_len);
+  TORCH_CHECK(k >= 1, "lambdarank_topk_grad: k must be at least 1, got ", k);
+  TORCH_CHECK(disc.device() == margin.device() &&
+                  disc.scalar_type() == torch::kFloat64 &&
+                  disc.is_contiguous() &&
+                  disc.numel() >= rank_pad_host(max_len),
+              "lambdarank_topk_grad: disc must be a float64 GPU table that "
+              "covers the longest group padded to a power of two");
+  TORCH_CHECK(variant >= 0 && variant <= 2 &&
+                  (variant != 1 || max_len <= WAVE),
+              "lambdarank_topk_grad: the wave variant serves groups of at "
+              "most 64 rows");
+  const int64_t n = margin.numel();
+  const int64_t G = group_ptr.numel() - 1;
+  auto out = torch::zeros({n, 2},
+      torch::TensorOptions().dtype(torch::kFloat32).device(margin.device()));
+  if (n == 0 || G <= 0) return out;
+  const int kk = (int)std::min<int64_t>(k, 1 << 30);
+  const bool wave =
+      variant == 1 || (variant == 0 && max_len <= WAVE && k >= 32);
+  if (ndcg)
+    launch_lambdarank_topk<true>(margin, label, group_ptr, disc, out, kk,
+                                 max_len, block, wave);
+  else
+    launch_lambdarank_topk<false>(margin, label, group_ptr, disc, out, kk,
+                                  max_len, block, wave);
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("lambdarank_topk_grad", &lambdarank_topk_grad,
+        "rank:pairwise / rank:ndcg pair gradients, top-k pair truncation",
+        py::arg("margin"), py::arg("label"), py::arg("group_ptr"),
+        py::arg("disc"), py::arg("k"), py::arg("ndcg"), py::arg("max_len"),
+        py::arg("block") = 0, py::arg("variant") = 0);
   m.def("rank_group_stats", &rank_group_stats,
         "per-group stable descending ranks + [dcg@k, idcg@k, idcg, ap]",
         py::arg("margin"), py::arg("label"), py::arg("group_ptr"),

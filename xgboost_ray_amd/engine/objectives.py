@@ -311,10 +311,19 @@ class LambdaRankBase(Objective):
 
     ndcg_weighting = False
     default_metric = "map"
+    # Pair truncation, set by the engine from lambdarank_pair_method and
+    # lambdarank_num_pair_per_sample: under "topk" a pair counts iff the
+    # better-ranked of its two rows stands in the first ``topk`` places of
+    # the stable descending margin order of its group.
+    pair_method = "all"
+    topk = 0
+    last_route = None
 
     def gradients(self, margin, label, weight=None, qid=None):
         if qid is None:
             raise ValueError("rank objectives require qid/group information")
+        if self.pair_method == "topk":
+            return self._gradients_topk(margin, label, weight, qid)
         if margin.device.type == "cuda":
             return self._gradients_gpu(margin, label, weight, qid)
         return self._gradients_generic(margin, label, weight, qid)
@@ -338,6 +347,13 @@ class LambdaRankBase(Objective):
             pos = diff_y > 0  # i more relevant than j
             if not bool(pos.any()):
                 continue
+            if self.pair_method == "topk":
+                # ranks as on the HIP path: stable, ties in row order
+                order = torch.argsort(m, descending=True, stable=True)
+                rank = torch.empty_like(order)
+                rank[order] = torch.arange(e - s, device=device)
+                pos = pos & (torch.minimum(
+                    rank.unsqueeze(1), rank.unsqueeze(0)) < self.topk)
             # every pair term in float64, from the score difference formed
             # in the margin's own precision - the HIP kernel's
             # (double)(mi - mj). In float32, 1 - rho cancels for a badly
@@ -414,6 +430,32 @@ class LambdaRankBase(Objective):
             g[s:e] += (-lam.sum(dim=1) + lam.sum(dim=0)).to(g.dtype)
             h[s:e] += (hess.sum(dim=1) + hess.sum(dim=0)).to(g.dtype)
         return self._apply_weight(g, h, weight)
+
+    def _gradients_topk(self, margin, label, weight, qid):
+        """lambdarank_pair_method="topk". On the GPU one HIP launch
+        (``ops.lambdarank_topk_grad``) sorts every group and runs the
+        truncated pair loop; CPU tensors, groups longer than
+        ``ops.RANK_LDS_MAX_GROUP`` and RXGB_RANK_GPU=0 take the generic
+        loop with the pair mask. ``last_route`` names the one that ran."""
+        if getattr(self, "map_weighting", False):
+            raise ValueError(
+                "lambdarank_pair_method='topk' is not supported with "
+                "rank:map; use rank:pairwise or rank:ndcg")
+        layout = rank_hip_layout(margin, qid)
+        if layout is None:
+            self.last_route = "torch"
+            return self._gradients_generic(margin, label, weight, qid)
+        from xgboost_ray_amd import ops
+
+        m = margin.contiguous().float()
+        gpair = ops.lambdarank_topk_grad(
+            m, label.contiguous().float(), layout[0],
+            ops.rank_disc_table(m.device), int(self.topk),
+            self.ndcg_weighting, max_len=layout[1])
+        self.last_route = "hip"
+        if weight is not None:
+            gpair = gpair * weight.unsqueeze(1)
+        return gpair
 
     def _gradients_gpu(self, margin, label, weight, qid):
         """HIP kernel path: one workgroup per query group, deterministic

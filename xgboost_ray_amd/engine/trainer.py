@@ -69,6 +69,10 @@ class TrainParams:
     aft_loss_distribution: str = "normal"
     aft_loss_distribution_scale: float = 1.0
     quantile_alpha: object = None  # float | list | "[a,b]" (reg:quantileerror)
+    # rank:pairwise / rank:ndcg pair truncation: "all", or "topk" with
+    # k = lambdarank_num_pair_per_sample (default 32)
+    lambdarank_pair_method: str = "all"
+    lambdarank_num_pair_per_sample: Optional[int] = None
     tree_method: str = "hist"
     booster: str = "gbtree"
     # DART (booster="dart") dropout parameters (xgboost semantics)
@@ -120,6 +124,34 @@ class TrainParams:
                 "sampling_method='gradient_based' is not supported with "
                 "reg:quantileerror: adaptive leaves take unweighted "
                 "residual quantiles of the sampled rows")
+        p.lambdarank_pair_method = p.lambdarank_pair_method or "all"
+        if p.lambdarank_pair_method not in ("all", "topk"):
+            raise ValueError(
+                "lambdarank_pair_method must be 'all' or 'topk' (sampled "
+                f"pairs, 'mean', are not supported), got "
+                f"{p.lambdarank_pair_method!r}")
+        k = p.lambdarank_num_pair_per_sample
+        if p.lambdarank_pair_method == "all":
+            if k is not None:
+                raise ValueError(
+                    "lambdarank_num_pair_per_sample needs "
+                    "lambdarank_pair_method='topk'; 'all' uses every pair")
+        else:
+            if p.objective == "rank:map":
+                raise ValueError(
+                    "lambdarank_pair_method='topk' is not supported with "
+                    "rank:map; use rank:pairwise or rank:ndcg")
+            k = 32 if k is None else k
+            try:  # parameter dicts often carry numbers as strings
+                kf = float(k)
+            except (TypeError, ValueError):
+                kf = 0.0
+            if isinstance(k, bool) or not (
+                    1.0 <= kf < 2.0**31 and kf == math.floor(kf)):
+                raise ValueError(
+                    "lambdarank_num_pair_per_sample must be an integer "
+                    f">= 1, got {k!r}")
+            p.lambdarank_num_pair_per_sample = int(kf)
         if isinstance(p.monotone_constraints, str):
             txt = p.monotone_constraints.strip().strip("()")
             p.monotone_constraints = [
@@ -300,11 +332,15 @@ class BoostingEngine:
         if (self.p.objective == "count:poisson"
                 and not self.p.max_delta_step):
             self.p.max_delta_step = 0.7
-        from xgboost_ray_amd.engine.objectives import AFT
+        from xgboost_ray_amd.engine.objectives import AFT, LambdaRankBase
 
         if isinstance(self.obj, AFT):
             self.obj.dist = str(self.p.aft_loss_distribution)
             self.obj.sigma = float(self.p.aft_loss_distribution_scale)
+        if (isinstance(self.obj, LambdaRankBase)
+                and self.p.lambdarank_pair_method == "topk"):
+            self.obj.pair_method = "topk"
+            self.obj.topk = self.p.lambdarank_num_pair_per_sample
         # output groups: classes, or one per quantile alpha
         self.n_class = max(
             1, self.p.num_class, getattr(self.obj, "n_target", 1)

@@ -519,6 +519,31 @@ def lambdamap_grad(margin, label, group_ptr, max_len=None, **kw):
                                         **kw)
 
 
+def lambdarank_topk_grad(margin, label, group_ptr, disc, k, ndcg,
+                         max_len=None, **kw):
+    """rank:pairwise (``ndcg`` false) / rank:ndcg gradient pairs f32 [n, 2]
+    (unweighted) with top-k pair truncation.
+
+    margin, label, group_ptr, disc, max_len as in ``rank_group_stats``;
+    k >= 1. With rank the stable descending order of the float32 margins
+    inside a group, a pair (i, j) with label_i > label_j counts iff
+    min(rank_i, rank_j) < k. A counted pair has
+    rho = 1 / (1 + exp(m_i - m_j)) (difference in float32, the rest
+    float64), hess = max(rho (1 - rho), 1e-16) and weight w = 1, or for ndcg
+    w = |dgain * ddisc| / idcg with gain = 2^label - 1, disc = disc[rank]
+    and idcg over the whole group, not truncated. It adds -rho w to g_i,
+    +rho w to g_j and hess w to both hessians. A group of fewer than two
+    rows and an ndcg group with idcg <= 0 give zeros; a row without a
+    counted pair gets exactly (0, 0); k >= the group's length is the
+    all-pairs gradient. Row weights are the caller's. NaN margins have no
+    defined result, but no address depends on a margin. On the GPU every
+    sum has a fixed order and nothing is atomic: equal inputs give equal
+    bytes.
+    """
+    return _impl(margin).lambdarank_topk_grad(
+        margin, label, group_ptr, disc, k, ndcg, max_len, **kw)
+
+
 def grad_fused(margin, label, weight, scale_pos_weight, mode):
     """Fused objective gradient + |g|/|h| max for the hot objectives
     (mode 0 = reg:squarederror, 1 = binary:logistic). GPU only: returns

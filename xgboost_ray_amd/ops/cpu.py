@@ -930,3 +930,47 @@ def lambdamap_grad(margin, label, group_ptr, max_len=None):
         out[s:e, 0] = -lam.sum(1) + lam.sum(0)
         out[s:e, 1] = hess.sum(1) + hess.sum(0)
     return torch.from_numpy(out.astype(np.float32))
+
+
+def lambdarank_topk_grad(margin, label, group_ptr, disc, k, ndcg,
+                         max_len=None):
+    """float64 numpy form of ``ops.lambdarank_topk_grad``: all pairs of a
+    group as [L, L] matrices, masked by min(rank_i, rank_j) < k."""
+    import numpy as np
+
+    m32 = np.asarray(_as_numpy(margin), np.float32)
+    y32 = np.asarray(_as_numpy(label), np.float32)
+    gp = np.asarray(_as_numpy(group_ptr), np.int64)
+    disc = np.asarray(_as_numpy(disc), np.float64)
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"lambdarank_topk_grad: k must be >= 1, got {k}")
+    out = np.zeros((len(m32), 2), np.float64)
+    for g in range(len(gp) - 1):
+        s, e = int(gp[g]), int(gp[g + 1])
+        L = e - s
+        if L < 2:
+            continue
+        m, y = m32[s:e], y32[s:e]
+        rank = np.empty(L, np.int64)
+        rank[_rank_order(m)] = np.arange(L)
+        win = (y[:, None] > y[None, :]) & (
+            np.minimum(rank[:, None], rank[None, :]) < k)
+        with np.errstate(over="ignore"):
+            rho = 1.0 / (1.0 + np.exp((m[:, None] - m[None, :]).astype(
+                np.float64)))
+        hess = np.maximum(rho * (1.0 - rho), 1e-16)
+        if ndcg:
+            gain = np.exp2(y.astype(np.float64)) - 1.0
+            idcg = (np.sort(gain)[::-1] * disc[:L]).sum()
+            if not idcg > 0.0:
+                continue
+            d = disc[rank]
+            w = np.abs((gain[:, None] - gain[None, :])
+                       * (d[:, None] - d[None, :])) / idcg
+            rho, hess = rho * w, hess * w
+        lam = np.where(win, rho, 0.0)
+        hess = np.where(win, hess, 0.0)
+        out[s:e, 0] = -lam.sum(1) + lam.sum(0)
+        out[s:e, 1] = hess.sum(1) + hess.sum(0)
+    return torch.from_numpy(out.astype(np.float32))

@@ -356,6 +356,17 @@ def lambdamap_grad(margin, label, group_ptr, max_len=None, block=0):
         int(block))
 
 
+def lambdarank_topk_grad(margin, label, group_ptr, disc, k, ndcg,
+                         max_len=None, block=0, variant=0):
+    """variant: 0 picks (a wave per group when the longest group has at
+    most 64 rows and k >= 32, else a workgroup per group), 1 / 2 force
+    one; block: workgroup size override. Both exist for the benchmark's
+    sweep."""
+    return _load_rank().lambdarank_topk_grad(
+        margin, label, group_ptr, disc, int(k), bool(ndcg),
+        _rank_max_len(group_ptr, max_len), int(block), int(variant))
+
+
 def update_margins(margin, ridx, starts, counts, leaf_values,
                    ridx_b=None, parity=None):
     # starts/counts/leaf_values stay on the HOST: the extension stages

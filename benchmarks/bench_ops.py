@@ -519,7 +519,113 @@ def bench_rank(shapes=((10_000_000, 100), (1_000_000, 1000),
         _os.environ.pop("RXGB_RANK_GPU")
 
 
+def bench_softmax(shapes=((11_000_000, 3), (11_000_000, 10),
+                          (1_000_000, 100), (1_000_000, None)),
+                  train_shape=(2_000_000, 28, 10)):
+    """The HIP multiclass kernels against the torch routes they replace, in
+    one process, windows alternating. The torch gradient line includes what
+    the trainer does with its result: K ``.contiguous()`` class slices and
+    2K ``abs().max()``. Rates are against the compulsory traffic, 4K + 4
+    bytes in and 8K out per row for the gradient, 4K + 4 in for the metric.
+    The last shape is one K above KC."""
+    from xgboost_ray_amd.engine.metrics import get_metric
+    from xgboost_ray_amd.engine.objectives import SoftProb
+    from xgboost_ray_amd.engine.trainer import BoostingEngine, EvalPack
+
+    dev = torch.device("cuda")
+    KC = ops.SOFTMAX_CHUNK_CLASSES
+
+    def show(name, t, nbytes=None):
+        rate = f"  {nbytes / t[0] / 1e9:8.3f} TB/s" if nbytes else ""
+        print(f"  {name:38s} {t[0]:9.3f} ms  [{t[1]:.3f}, {t[2]:.3f}]{rate}",
+              flush=True)
+
+    def switches(on):
+        for name in ("RXGB_FUSED_GRAD", "RXGB_FUSED_EVAL"):
+            if on:
+                _os.environ.pop(name, None)
+            else:
+                _os.environ[name] = "0"
+
+    for n, K in shapes:
+        K = K or KC + 1
+        gen = torch.Generator(device=dev).manual_seed(7)
+        margin = torch.randn(n, K, device=dev, generator=gen) * 3
+        label = torch.randint(0, K, (n,), device=dev, generator=gen).float()
+        obj, metrics = SoftProb(K), [get_metric("mlogloss"),
+                                     get_metric("merror")]
+        print(f"softmax: {n} x {K} (KC = {KC})")
+
+        def grad(on):
+            def run():
+                switches(on)
+                gp = obj.gradients(margin, label)
+                mx = getattr(gp, "_rxgb_absmax_cls", None)
+                for c in range(K):  # the trainer's use of the result
+                    sl = gp[:, c, :].contiguous()
+                    if mx is None:
+                        sl[:, 0].abs().max(), sl[:, 1].abs().max()
+            return run
+
+        def metric(on):
+            def run():
+                switches(on)
+                for m in metrics:
+                    m.local_stats(margin, label, None, None, obj)
+            return run
+
+        g_bytes, e_bytes = n * (12 * K + 4), n * (4 * K + 4)
+        hip, tor = _spread_alt([grad(True), grad(False)])
+        show("softmax_grad [hip]", hip, g_bytes)
+        show("gradients + slices + maxima [torch]", tor)
+        hip, tor = _spread_alt([metric(True), metric(False)])
+        show("mlogloss + merror [hip, 2 launches]", hip, 2 * e_bytes)
+        show("mlogloss + merror [torch]", tor)
+        switches(True)
+        # tile constants: rows R and chunk KC that the launch may take
+        for chunk in (16, 32, 64):
+            for rows in (64, 128, 192, 256):
+                try:
+                    t = _spread(lambda: ops.softmax_grad(
+                        margin, label, chunk=chunk, rows=rows))
+                except RuntimeError:
+                    continue  # this tile does not fit the LDS budget
+                show(f"softmax_grad chunk {chunk} rows {rows}", t, g_bytes)
+        del margin, label
+
+    n, F, K = train_shape
+    gen = torch.Generator(device=dev).manual_seed(9)
+    X = torch.randn(n, F, device=dev, generator=gen)
+    y = torch.bucketize(X[:, 0] + 0.5 * X[:, 1],
+                        torch.linspace(-1.5, 1.5, K - 1, device=dev)).float()
+    dm = BinnedMatrix.build(X, label=y, max_bin=256)
+    del X
+    print(f"multi:softprob round, {n} x {F}, K = {K}, depth 6, mlogloss "
+          f"every round; 10 rounds after 2 of warm-up")
+    for run in range(2):
+        for on in (True, False):
+            switches(on)
+            eng = BoostingEngine(
+                {"objective": "multi:softprob", "num_class": K,
+                 "max_depth": 6, "tree_method": "gpu_hist",
+                 "eval_metric": ["mlogloss"]}, dm)
+            for it in range(12):
+                if it == 2:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                eng.update()
+                loss = eng.eval_sets([EvalPack(name="train", X=None)])
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) / 10 * 1e3
+            print(f"  run {run} [{'hip' if on else 'torch'}] {ms:9.3f} "
+                  f"ms/round  mlogloss {loss['train']['mlogloss']:.6f}",
+                  flush=True)
+    switches(True)
+
+
 def main():
+    if _sys.argv[1:2] == ["softmax"]:
+        return bench_softmax()
     if _sys.argv[1:2] == ["rank"]:
         return bench_rank()
     if _sys.argv[1:2] == ["leaf_quantile"]:

@@ -56,6 +56,22 @@ if "--cpu-only" not in sys.argv:
                                  "-Xclang", "-packed-fp32-ops"],
                     },
                 ),
+                # The multiclass kernels, again a module of their own with
+                # the same opt-out: their float32 work is one weight
+                # multiply per value and the maxima.
+                cpp_extension.CUDAExtension(
+                    name="xgboost_ray_amd._hip_softmax_ops",
+                    sources=[os.path.join(src_dir, "multi",
+                                          "softmax_ops.hip")],
+                    extra_compile_args={
+                        "cxx": ["-O3", "-std=c++17"],
+                        # -ffp-contract=off: a row's float64 steps are the
+                        # contract's, none fused with its neighbour
+                        "nvcc": ["-O3", "-std=c++17", "-ffp-contract=off",
+                                 "-Xclang", "-target-feature",
+                                 "-Xclang", "-packed-fp32-ops"],
+                    },
+                ),
             ]
             cmdclass = {"build_ext": cpp_extension.BuildExtension}
     except Exception as e:  # pragma: no cover

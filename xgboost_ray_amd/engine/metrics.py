@@ -205,10 +205,26 @@ class AUCPR(Metric):
         return float((p * dr).sum())
 
 
+def _fused_multiclass(margin, label, weight):
+    """``ops.eval_multiclass`` sums f64 [sum w*nll, sum w*wrong, sum w] when
+    the margin is a 2-D GPU tensor (RXGB_FUSED_EVAL=0 disables), else None."""
+    import os
+
+    if (not margin.is_cuda or margin.dim() != 2
+            or os.environ.get("RXGB_FUSED_EVAL") == "0"):
+        return None
+    from xgboost_ray_amd import ops
+
+    return ops.eval_multiclass(margin, label, weight)
+
+
 class MLogLoss(Metric):
     name = "mlogloss"
 
     def local_stats(self, margin, label, weight, qid, obj):
+        fused = _fused_multiclass(margin, label, weight)
+        if fused is not None:
+            return fused[::2]
         logp = torch.log_softmax(margin.double(), dim=1)
         w = _w(label, weight)
         ll = -logp[torch.arange(len(label), device=margin.device), label.long()]
@@ -222,6 +238,9 @@ class MError(Metric):
     name = "merror"
 
     def local_stats(self, margin, label, weight, qid, obj):
+        fused = _fused_multiclass(margin, label, weight)
+        if fused is not None:
+            return fused[1:]
         pred = margin.argmax(dim=1)
         w = _w(label, weight)
         wrong = (pred != label.long()).double()

@@ -227,7 +227,25 @@ class SoftmaxBase(Objective):
             raise ValueError("multi objectives need num_class >= 2")
         self.n_class = n_class
 
+    last_route = None
+
     def gradients(self, margin, label, weight=None, qid=None):
+        """[n, k, 2] pairs. A GPU margin takes ``ops.softmax_grad`` (one HIP
+        pass, class-major storage, per-class maxima as ``_rxgb_absmax_cls``
+        for the trainer's class slices); the torch composition below serves
+        CPU tensors and RXGB_FUSED_GRAD=0. ``last_route`` names the one
+        that ran."""
+        import os
+
+        if (margin.is_cuda and margin.dim() == 2
+                and os.environ.get("RXGB_FUSED_GRAD") != "0"):
+            from xgboost_ray_amd import ops
+
+            gp, mx = ops.softmax_grad(margin, label, weight)
+            gp._rxgb_absmax_cls = mx
+            self.last_route = "hip"
+            return gp
+        self.last_route = "torch"
         # margin: [n, k]
         p = torch.softmax(margin, dim=1)
         y = torch.nn.functional.one_hot(label.long(), self.n_class).to(p.dtype)

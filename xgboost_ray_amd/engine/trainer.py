@@ -624,8 +624,14 @@ class BoostingEngine:
             self.iteration += 1
             return []
         trees, classes = [], []
+        # per-class maxima from ops.softmax_grad: each class slice carries
+        # its own, so _quantize / _mvs_sample skip their reductions
+        mx_cls = getattr(gpair, "_rxgb_absmax_cls", None)
         for cls in range(self.n_class):
             gp = gpair if self.n_class == 1 else gpair[:, cls, :]
+            if mx_cls is not None:
+                # the slice is contiguous, so gp.contiguous() below is gp
+                gp._rxgb_absmax = mx_cls[cls]
             # num_parallel_tree > 1: boosted random forest - k trees per
             # round on the same gradients with independent row/column
             # samples (XGBoost GBTree::BoostNewTrees semantics)
@@ -661,8 +667,11 @@ class BoostingEngine:
         alpha = float(self.p.reg_alpha)
         eta = float(self.p.eta)
         deltas = []
+        mx_cls = getattr(gpair, "_rxgb_absmax_cls", None)
         for cls in range(self.n_class):
             gp = gpair if self.n_class == 1 else gpair[:, cls, :]
+            if mx_cls is not None:
+                gp._rxgb_absmax = mx_cls[cls]
             # chunked fp64 accumulation: fixed chunk order -> identical
             # sums on every rank layout of the same data
             sg = torch.zeros(F, dtype=torch.float64, device=self.device)

@@ -556,3 +556,50 @@ def grad_fused(margin, label, weight, scale_pos_weight, mode):
     from xgboost_ray_amd.ops import gpu
 
     return gpu.grad_fused(margin, label, weight, scale_pos_weight, mode)
+
+
+# KC of the GPU multiclass kernels: a margin with K <= KC classes is one LDS
+# chunk per row tile, a wider one is walked in chunks of KC
+SOFTMAX_CHUNK_CLASSES = _cpu.SOFTMAX_CHUNK_CLASSES
+
+
+def softmax_grad(margin, label, weight=None, **kw):
+    """multi:softprob / multi:softmax gradient pairs and their per-class
+    maxima, one pass over the margin.
+
+    margin: f32 [n, K] contiguous, K >= 2; label: f32 [n] class indices;
+    weight: f32 [n] or None. Returns (gpair, absmax): gpair f32 of shape
+    [n, K, 2], stored class-major ([K, n, 2], permuted), so every
+    ``gpair[:, cls, :]`` is contiguous; absmax f32 [K, 2] with
+    absmax[cls, c] == gpair[:, cls, c].abs().max() bitwise.
+
+    Per row, in float64 from the float32 inputs and with no step fused into
+    the next: m = max_k x_k (compared in float32), d_k = x_k - m,
+    e_k = exp(d_k), s = sum_k e_k in ascending class order, p_k = e_k / s,
+    g_k = float32(p_k - [k == y]), h_k = float32(max(2 p_k (1 - p_k),
+    1e-16)); with a weight both are then multiplied by it in float32. The
+    label, truncated toward zero as ``.long()`` does, is only compared with
+    k and never forms an address: outside [0, K) it gives g_k = p_k. A NaN
+    margin makes its row's outputs NaN, and absmax keeps the NaN.
+
+    On the GPU a margin with K > SOFTMAX_CHUNK_CLASSES is walked in
+    chunks and s is a running sum, rescaled by exp(m_old - m_new) whenever
+    the running maximum grows: such a K is held to the error bound
+    |out - ref| <= 2^-23 |ref| + 2^-40 max(1, w), not to the bits of the
+    plain sum. Each K takes one route and nothing is atomic: equal inputs
+    give equal bytes. ``ops.cpu.softmax_grad`` is the numpy float64 form and
+    the oracle. The torch composition in ``SoftmaxBase.gradients`` remains
+    the CPU training path.
+    """
+    return _impl(margin).softmax_grad(margin, label, weight, **kw)
+
+
+def eval_multiclass(margin, label, weight=None, **kw):
+    """f64 [3] = [sum w * nll, sum w * wrong, sum w] of a multiclass margin
+    (inputs as in ``softmax_grad``; w = 1 without weights). Per row in
+    float64, with m, d and s as in ``softmax_grad``: nll = log(s) - d_y (NaN
+    for a label outside [0, K)); wrong = 1 unless the lowest index attaining
+    the maximum equals the label. On the GPU the sums run in a fixed order
+    (a thread's rows in order, a butterfly inside a wave, wave order, then a
+    sum over the workgroups' partials)."""
+    return _impl(margin).eval_multiclass(margin, label, weight, **kw)

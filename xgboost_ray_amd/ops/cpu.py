@@ -974,3 +974,71 @@ def lambdarank_topk_grad(margin, label, group_ptr, disc, k, ndcg,
         out[s:e, 0] = -lam.sum(1) + lam.sum(0)
         out[s:e, 1] = hess.sum(1) + hess.sum(0)
     return torch.from_numpy(out.astype(np.float32))
+
+
+# ---------------------------------------------------------------------------
+# Multiclass: the softmax gradient and the mlogloss / merror sums (contract:
+# docs/parity.md "Multiclass on the device"). Plain numpy float64 - the twins
+# of the HIP kernels and their oracle, not the CPU training path.
+# ---------------------------------------------------------------------------
+# classes per LDS chunk of the HIP kernels (K <= KC: one chunk per row tile)
+SOFTMAX_CHUNK_CLASSES = 16
+
+
+def _softmax_rows(margin, label):
+    """(d = x - max, e = exp(d), s = ascending sum of e, label class or -1)
+    of every row, float64 from the float32 inputs."""
+    import numpy as np
+
+    x = np.asarray(_as_numpy(margin), np.float32)
+    if x.ndim != 2 or x.shape[1] < 2:
+        raise ValueError("multiclass ops need a margin [n, K] with K >= 2")
+    y = np.asarray(_as_numpy(label), np.float32)
+    K = x.shape[1]
+    with np.errstate(invalid="ignore"):
+        d = x.astype(np.float64) - x.max(axis=1, keepdims=True).astype(
+            np.float64)
+        e = np.exp(d)
+        # truncated toward zero as .long() does; outside [0, K): no class
+        yi = np.where((y > -1) & (y < K), np.trunc(y), -1).astype(np.int64)
+    s = np.zeros(len(x), np.float64)
+    for k in range(K):  # ascending class order, not numpy's pairwise sum
+        s = s + e[:, k]
+    return d, e, s, yi
+
+
+def softmax_grad(margin, label, weight=None):
+    import numpy as np
+
+    d, e, s, yi = _softmax_rows(margin, label)
+    n, K = e.shape
+    with np.errstate(invalid="ignore"):
+        p = e / s[:, None]
+        hit = yi[:, None] == np.arange(K)[None, :]
+        g = (p - hit).astype(np.float32)
+        h = np.maximum(2.0 * p * (1.0 - p), 1e-16).astype(np.float32)
+        if weight is not None:
+            w = np.asarray(_as_numpy(weight), np.float32)[:, None]
+            g, h = g * w, h * w  # float32: the second rounding
+    store = np.stack([g.T, h.T], axis=-1)  # class-major [K, n, 2]
+    absmax = (np.abs(store).max(axis=1) if n
+              else np.zeros((K, 2), np.float32))
+    return (torch.from_numpy(np.ascontiguousarray(store)).permute(1, 0, 2),
+            torch.from_numpy(absmax.astype(np.float32)))
+
+
+def eval_multiclass(margin, label, weight=None):
+    import numpy as np
+
+    d, e, s, yi = _softmax_rows(margin, label)
+    n = len(s)
+    w = (np.ones(n, np.float64) if weight is None
+         else np.asarray(_as_numpy(weight), np.float32).astype(np.float64))
+    rows = np.arange(n)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        nll = np.where(yi >= 0, np.log(s) - d[rows, np.maximum(yi, 0)],
+                       np.nan)
+    # the lowest index attaining the maximum is where d first reaches 0
+    wrong = (np.argmax(d == 0.0, axis=1) != yi).astype(np.float64)
+    return torch.from_numpy(
+        np.array([(w * nll).sum(), (w * wrong).sum(), w.sum()], np.float64))

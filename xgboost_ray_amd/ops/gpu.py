@@ -367,6 +367,44 @@ def lambdarank_topk_grad(margin, label, group_ptr, disc, k, ndcg,
         _rank_max_len(group_ptr, max_len), int(block), int(variant))
 
 
+SOFTMAX_CHUNK_CLASSES = 16  # checked against the extension's own constant
+_softmax_ext = None
+
+
+def _load_softmax():
+    """The multiclass kernels' module (csrc/multi); required like
+    ``_hip_ops``."""
+    global _softmax_ext
+    if _softmax_ext is None:
+        _load()  # same build; raises the build hint if nothing is built
+        import importlib
+
+        _softmax_ext = importlib.import_module(
+            "xgboost_ray_amd._hip_softmax_ops")
+        assert _softmax_ext.SOFTMAX_CHUNK_CLASSES == SOFTMAX_CHUNK_CLASSES
+    return _softmax_ext
+
+
+def _softmax_args(margin, label, weight):
+    w = weight.contiguous().float() if weight is not None else torch.zeros(
+        0, dtype=torch.float32, device=margin.device)
+    return margin.contiguous().float(), label.contiguous().float(), w
+
+
+def softmax_grad(margin, label, weight=None, chunk=0, rows=0):
+    """chunk / rows override KC and the tile's rows (benchmarks/bench_ops.py
+    sweeps them)."""
+    store, absmax = _load_softmax().softmax_grad(
+        *_softmax_args(margin, label, weight), int(chunk), int(rows))
+    # stored class-major [K, n, 2]: every gpair[:, cls, :] is contiguous
+    return store.permute(1, 0, 2), absmax
+
+
+def eval_multiclass(margin, label, weight=None, chunk=0, rows=0):
+    return _load_softmax().eval_multiclass(
+        *_softmax_args(margin, label, weight), int(chunk), int(rows))
+
+
 def update_margins(margin, ridx, starts, counts, leaf_values,
                    ridx_b=None, parity=None):
     # starts/counts/leaf_values stay on the HOST: the extension stages

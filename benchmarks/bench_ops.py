@@ -623,7 +623,120 @@ def bench_softmax(shapes=((11_000_000, 3), (11_000_000, 10),
     switches(True)
 
 
+def bench_survival(sizes=(1_000_000, 10_000_000),
+                   train_shape=(2_000_000, 28)):
+    """The HIP survival kernels against the torch routes they replace, on the
+    same tensors in one process, windows alternating. The torch gradient
+    lines include the two ``abs().max()`` that ``_quantize`` then needs. Cox:
+    distinct times, and ties in runs of about 10; AFT (normal): 30 %
+    right-censored, and an even mix of the four kinds. Then one full round
+    of each objective with and without the switches."""
+    from xgboost_ray_amd.engine.metrics import get_metric
+    from xgboost_ray_amd.engine.objectives import AFT, Cox
+    from xgboost_ray_amd.engine.trainer import BoostingEngine, EvalPack
+
+    dev = torch.device("cuda")
+
+    def show(name, t):
+        print(f"  {name:38s} {t[0]:9.3f} ms  [{t[1]:.3f}, {t[2]:.3f}]",
+              flush=True)
+
+    def switches(on):
+        for name in ("RXGB_FUSED_GRAD", "RXGB_FUSED_EVAL"):
+            if on:
+                _os.environ.pop(name, None)
+            else:
+                _os.environ[name] = "0"
+
+    def routes(obj, metric, margin, label):
+        def grad(on):
+            def run():
+                switches(on)
+                gp = obj.gradients(margin, label)
+                if getattr(gp, "_rxgb_absmax", None) is None:
+                    gp[:, 0].abs().max(), gp[:, 1].abs().max()
+            return run
+
+        def ev(on):
+            def run():
+                switches(on)
+                metric.local_stats(margin, label, None, None, obj)
+            return run
+
+        hip, tor = _spread_alt([grad(True), grad(False)])
+        show(f"{obj.name} gradients [hip]", hip)
+        show(f"{obj.name} gradients + maxima [torch]", tor)
+        hip, tor = _spread_alt([ev(True), ev(False)])
+        show(f"{metric.name} [hip]", hip)
+        show(f"{metric.name} [torch]", tor)
+        switches(True)
+
+    for n in sizes:
+        gen = torch.Generator(device=dev).manual_seed(7)
+        margin = torch.randn(n, device=dev, generator=gen) * 2
+        u = torch.rand(n, device=dev, generator=gen)
+        sign = torch.where(torch.rand(n, device=dev, generator=gen) < 0.7,
+                           1.0, -1.0)
+        for what, t in (("distinct times",
+                         torch.randperm(n, device=dev, generator=gen) + 1.0),
+                        ("ties in runs of ~10",
+                         torch.floor(u * (n // 10)) + 1.0)):
+            print(f"survival:cox, {n} rows, {what} "
+                  f"(tile {ops.COX_TILE_ROWS})")
+            routes(Cox(), get_metric("cox-nloglik"), margin, t * sign)
+        lo = torch.exp(torch.randn(n, device=dev, generator=gen))
+        for what, kind in (("30 % right-censored", (u < 0.3).long()),
+                           ("even mix of the four kinds",
+                            (u * 4).long().clamp(max=3))):
+            hi = torch.where(kind == 1, float("inf"),
+                             torch.where(kind == 3, lo * 2.5, lo))
+            label = torch.stack(
+                [torch.where(kind == 2, 0.0, lo),
+                 torch.where(kind == 2, lo, hi)], dim=1).contiguous()
+            print(f"survival:aft (normal), {n} rows, {what}")
+            routes(AFT(), get_metric("aft-nloglik"), margin, label)
+
+    n, F = train_shape
+    gen = torch.Generator(device=dev).manual_seed(9)
+    X = torch.randn(n, F, device=dev, generator=gen)
+    t = torch.exp(0.7 * X[:, 0] + 0.3 * torch.randn(n, device=dev,
+                                                    generator=gen))
+    cens = torch.rand(n, device=dev, generator=gen) < 0.3
+    dm = BinnedMatrix.build(X, max_bin=256)
+    del X
+    for objective, metric in (("survival:cox", "cox-nloglik"),
+                              ("survival:aft", "aft-nloglik")):
+        if objective == "survival:cox":
+            dm.label = torch.where(cens, -t, t)
+        else:
+            dm.label = None
+            dm.label_lower_bound = t
+            dm.label_upper_bound = torch.where(cens, float("inf"), t)
+        print(f"{objective} round, {n} x {F}, depth 6, {metric} every "
+              f"round; 10 rounds after 2 of warm-up")
+        for run in range(2):
+            for on in (True, False):
+                switches(on)
+                eng = BoostingEngine(
+                    {"objective": objective, "max_depth": 6,
+                     "tree_method": "gpu_hist"}, dm)
+                for it in range(12):
+                    if it == 2:
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                    eng.update()
+                    loss = eng.eval_sets([EvalPack(name="train", X=None)])
+                torch.cuda.synchronize()
+                ms = (time.perf_counter() - t0) / 10 * 1e3
+                print(f"  run {run} [{'hip' if on else 'torch'}] {ms:9.3f} "
+                      f"ms/round  {metric} {loss['train'][metric]:.6f}",
+                      flush=True)
+    switches(True)
+
+
 def main():
+    if _sys.argv[1:2] == ["survival"]:
+        return bench_survival()
     if _sys.argv[1:2] == ["softmax"]:
         return bench_softmax()
     if _sys.argv[1:2] == ["rank"]:

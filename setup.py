@@ -72,6 +72,22 @@ if "--cpu-only" not in sys.argv:
                                  "-Xclang", "-packed-fp32-ops"],
                     },
                 ),
+                # The survival kernels (AFT, Cox), a module of their own
+                # with the same flags: their float32 work is the weight
+                # multiply and the maxima.
+                cpp_extension.CUDAExtension(
+                    name="xgboost_ray_amd._hip_survival_ops",
+                    sources=[os.path.join(src_dir, "survival",
+                                          "survival_ops.hip")],
+                    extra_compile_args={
+                        "cxx": ["-O3", "-std=c++17"],
+                        # -ffp-contract=off: a row's float64 steps and the
+                        # scans' adds are the contract's, none fused
+                        "nvcc": ["-O3", "-std=c++17", "-ffp-contract=off",
+                                 "-Xclang", "-target-feature",
+                                 "-Xclang", "-packed-fp32-ops"],
+                    },
+                ),
             ]
             cmdclass = {"build_ext": cpp_extension.BuildExtension}
     except Exception as e:  # pragma: no cover

@@ -426,6 +426,10 @@ class AFTNLogLik(Metric):
         from xgboost_ray_amd.engine.objectives import AFT
 
         o = obj if isinstance(obj, AFT) else AFT()
+        if _fused_eval_ok(margin):
+            from xgboost_ray_amd import ops
+
+            return ops.eval_aft(margin, label, weight, o.dist, o.sigma)
         nll = o.nll(margin.double(), label[:, 0].double(),
                     label[:, 1].double())
         w = _w(label[:, 0], weight)
@@ -443,6 +447,10 @@ class CoxNLogLik(Metric):
     higher_better = False
 
     def local_stats(self, margin, label, weight, qid, obj):
+        if _fused_eval_ok(margin):
+            from xgboost_ray_amd import ops
+
+            return ops.eval_cox(margin, ops.cox_layout(label))
         t = label.abs().double()
         event = label > 0
         m = margin.double()

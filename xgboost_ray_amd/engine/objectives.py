@@ -737,6 +737,14 @@ class SquaredLogError(Objective):
             raise ValueError("reg:squaredlogerror requires label > -1")
 
 
+def _fused_survival_ok(margin):
+    """The HIP survival kernels serve a GPU margin vector unless
+    RXGB_FUSED_GRAD=0."""
+    import os
+
+    return (margin.is_cuda and margin.dim() == 1
+            and os.environ.get("RXGB_FUSED_GRAD") != "0")
+
 
 class AFT(Objective):
     """survival:aft - accelerated failure time with interval censoring.
@@ -854,7 +862,22 @@ class AFT(Objective):
             drh = rh * (-z - rh)
         return rh, drh
 
+    last_route = None
+
     def gradients(self, margin, label, weight=None, qid=None):
+        """A GPU margin takes ``ops.aft_grad`` (one HIP pass, a row runs its
+        own censoring branch only, maxima as ``_rxgb_absmax``); the torch
+        composition below serves CPU tensors and RXGB_FUSED_GRAD=0.
+        ``last_route`` names the one that ran."""
+        if _fused_survival_ok(margin):
+            from xgboost_ray_amd import ops
+
+            gp, mx = ops.aft_grad(margin, label, weight, self.dist,
+                                  self.sigma)
+            gp._rxgb_absmax = mx  # consumed by _quantize
+            self.last_route = "hip"
+            return gp
+        self.last_route = "torch"
         # label is [n, 2]: (lower, upper); all math in f64 - the censored
         # branches divide underflow-prone densities
         yl, yu = label[:, 0].double(), label[:, 1].double()
@@ -932,13 +955,26 @@ class Cox(Objective):
     label < 0 is right-censored at t=|label|. Risk sets are computed over
     the local shard (xgboost's distributed behavior); margins are
     log-hazard ratios, predictions exp(margin). All ops are sorted
-    cumsums - deterministic on CPU and GPU, no custom kernels.
+    cumsums. A GPU margin takes ``ops.cox_grad``: HIP kernels that reduce,
+    then scan, in both directions over a time order cached on the label
+    tensor (``ops.cox_layout``), with the maxima as ``_rxgb_absmax``. The
+    torch composition serves CPU tensors and RXGB_FUSED_GRAD=0; both are
+    deterministic. ``last_route`` names the one that ran.
     """
 
     name = "survival:cox"
     default_metric = "cox-nloglik"
+    last_route = None
 
     def gradients(self, margin, label, weight=None, qid=None):
+        if _fused_survival_ok(margin):
+            from xgboost_ray_amd import ops
+
+            gp, mx = ops.cox_grad(margin, ops.cox_layout(label), weight)
+            gp._rxgb_absmax = mx  # consumed by _quantize
+            self.last_route = "hip"
+            return gp
+        self.last_route = "torch"
         t = label.abs().double()
         event = (label > 0).double()
         m = margin.double()

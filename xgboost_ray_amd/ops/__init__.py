@@ -603,3 +603,74 @@ def eval_multiclass(margin, label, weight=None, **kw):
     (a thread's rows in order, a butterfly inside a wave, wave order, then a
     sum over the workgroups' partials)."""
     return _impl(margin).eval_multiclass(margin, label, weight, **kw)
+
+
+# Sorted positions per workgroup of the GPU Cox kernels (asserted equal to
+# the module's on load): the sizes around it are where their paths change
+COX_TILE_ROWS = _cpu.COX_TILE_ROWS
+
+
+def aft_grad(margin, label, weight, dist, sigma):
+    """survival:aft gradient pairs and their maxima, one pass.
+
+    margin: f32 [n]; label: f32 [n, 2] (lower, upper); weight: f32 [n] or
+    None; dist: "normal", "logistic" or "extreme"; sigma: host float.
+    Returns (gpair f32 [n, 2], absmax f32 [2]) with absmax[c] ==
+    gpair[:, c].abs().max() bitwise.
+
+    Per row, in float64 from the float32 inputs, the contract of
+    ``AFT.gradients``: lo = log(max(yl, 1e-16)), hi likewise, zl and zu
+    clamped to [-15, 15]; the row is uncensored if yl == yu, else
+    right-censored if isinf(yu), else left-censored if yl <= 0, else an
+    interval; D >= 1e-300 and h >= 1e-6; g and h are cast to float32 and
+    then multiplied by the weight in float32. The normal distribution goes
+    through erfc (S(z) = erfc(z / sqrt 2) / 2). On the GPU a row evaluates
+    its own branch only, and the maxima leave the kernel without atomics.
+    A NaN margin makes its row's pair NaN, and absmax keeps the NaN.
+    ``ops.cpu.aft_grad`` is the float64 torch form and the oracle."""
+    return _impl(margin).aft_grad(margin, label, weight, dist, sigma)
+
+
+def eval_aft(margin, label, weight, dist, sigma):
+    """f64 [2] = [sum w * nll, sum w] with nll as ``AFT.nll`` (inputs as in
+    ``aft_grad``; w = 1 without weights); fixed-order sums on the GPU."""
+    return _impl(margin).eval_aft(margin, label, weight, dist, sigma)
+
+
+def cox_layout(label):
+    """What survival:cox needs of its labels alone (``ops.cpu.cox_layout``):
+    built once per label tensor and cached on it as ``_rxgb_cox_layout``,
+    keyed on its ``_version`` and device, as ``_rxgb_rank_layout`` is on
+    qid. A caller that passes the same tensor object every round, as the
+    trainer does, pays the sort once per data set."""
+    hit = getattr(label, "_rxgb_cox_layout", None)
+    if hit is not None and hit[:2] == (label._version, label.device):
+        return hit[2]
+    lay = _impl(label).cox_layout(label)
+    label._rxgb_cox_layout = (label._version, label.device, lay)
+    return lay
+
+
+def cox_grad(margin, layout, weight=None):
+    """survival:cox (Breslow) gradient pairs and their maxima.
+
+    margin: f32 [n]; layout: ``cox_layout(label)``; weight: f32 [n] or None.
+    Returns (gpair f32 [n, 2] in row order, absmax f32 [2]). With s a row's
+    sorted position: shift = max margin (float32), eta = exp(double(m) -
+    shift), R_s = max(C[last(s)], 1e-300) with C the inclusive prefix sum of
+    eta, a = ev / R, b = ev / R^2, A_s = SufA[first(s)] with SufA the
+    inclusive suffix sum of a (B likewise), g = -ev + eta A, h = max(eta A -
+    eta^2 B, 1e-6); cast to float32, then the weight in float32. A NaN
+    margin makes every output NaN. On the GPU the sums are a reduce-then-
+    scan over tiles of COX_TILE_ROWS positions, in both directions, with
+    one fixed grouping: equal inputs give equal bytes. The grouping is not
+    the sequential one, so the GPU is held to the error bound of
+    docs/parity.md, not to the oracle's bits."""
+    return _impl(margin).cox_grad(margin, layout, weight)
+
+
+def eval_cox(margin, layout):
+    """f64 [2] = [-ll, number of events] of cox-nloglik: ll sums, over event
+    rows, m - shift - log(max(C_s, 1e-300)) (C_s itself, not tie-adjusted,
+    as ``CoxNLogLik`` has it)."""
+    return _impl(margin).eval_cox(margin, layout)

@@ -1042,3 +1042,199 @@ def eval_multiclass(margin, label, weight=None):
     wrong = (np.argmax(d == 0.0, axis=1) != yi).astype(np.float64)
     return torch.from_numpy(
         np.array([(w * nll).sum(), (w * wrong).sum(), w.sum()], np.float64))
+
+
+# --- survival (contract: docs/parity.md "Survival on the device") ----------
+# Float64 torch forms written from the formulae, not from the objective
+# classes; tests/test_survival_ops_cpu.py pins them to those classes.
+
+COX_TILE_ROWS = 2048  # sorted positions per workgroup of the GPU Cox kernels
+AFT_DISTS = ("normal", "logistic", "extreme")
+
+
+def _aft_terms(dist, z):
+    """(f, dlogf, S, F) of the clamped z: density, d log f / dz, survival in
+    its no-cancellation form, and the cdf as the metric takes it."""
+    if dist == "logistic":
+        s = 1.0 / (1.0 + torch.exp(-z))
+        return s * (1.0 - s), 1.0 - 2.0 * s, 1.0 / (1.0 + torch.exp(z)), s
+    if dist == "extreme":
+        ez = torch.exp(torch.clamp(z, max=15.0))
+        S = torch.exp(-ez)
+        return ez * S, 1.0 - ez, S, 1.0 - S
+    if dist != "normal":
+        raise ValueError(f"unknown AFT distribution {dist!r}")
+    r = 0.7071067811865476  # 1 / sqrt(2)
+    f = torch.exp(-0.5 * z * z) / 2.5066282746310002  # sqrt(2 pi)
+    return (f, -z, 0.5 * torch.special.erfc(z * r),
+            0.5 * torch.special.erfc(-z * r))
+
+
+def _aft_rows(margin, label, sigma):
+    yl, yu = label[:, 0].float(), label[:, 1].float()
+    m = margin.float().double()
+    lo = torch.log(torch.clamp(yl.double(), min=1e-16))
+    hi = torch.log(torch.clamp(yu.double(), min=1e-16))
+    zl = torch.clamp((lo - m) / sigma, min=-15.0, max=15.0)
+    zu = torch.clamp((hi - m) / sigma, min=-15.0, max=15.0)
+    unc = yl == yu
+    right = torch.isinf(yu) & ~unc
+    left = (yl <= 0) & ~unc & ~right
+    return lo, zl, zu, unc, right, left
+
+
+def _weighted_pair(g, h, weight):
+    g, h = g.float(), h.float()
+    if weight is not None:
+        g, h = g * weight.float(), h * weight.float()  # second rounding
+    gp = torch.stack([g, h], dim=-1)
+    absmax = (gp.abs().amax(0) if len(gp)
+              else torch.zeros(2, dtype=torch.float32))
+    return gp, absmax
+
+
+def aft_grad(margin, label, weight, dist, sigma):
+    sig = float(sigma)
+    s2 = sig * sig
+    lo, zl, zu, unc, right, left = _aft_rows(margin, label, sig)
+    fl, dl, Sl, _ = _aft_terms(dist, zl)
+    fu, du, Su, Fu = _aft_terms(dist, zu)
+    # uncensored
+    g = dl / sig
+    if dist == "logistic":
+        s = 1.0 / (1.0 + torch.exp(-zl))
+        h = 2.0 * s * (1.0 - s) / s2
+    elif dist == "extreme":
+        h = torch.exp(torch.clamp(zl, max=15.0)) / s2
+    else:
+        h = torch.full_like(zl, 1.0 / s2)
+    # right-censored: hazard f / S at zl
+    if dist == "logistic":
+        hz = 1.0 / (1.0 + torch.exp(-zl))
+        dhz = hz * (1.0 - hz)
+    elif dist == "extreme":
+        hz = torch.exp(torch.clamp(zl, max=15.0))
+        dhz = hz
+    else:
+        hz = fl / torch.clamp(Sl, min=1e-300)
+        dhz = hz * (hz - zl)
+    g = torch.where(right, -hz / sig, g)
+    h = torch.where(right, dhz / s2, h)
+    # left-censored: reversed hazard f / F at zu
+    if dist == "logistic":
+        rh = Su
+        drh = -rh * (1.0 - rh)
+    elif dist == "extreme":
+        rh = fu / torch.clamp(1.0 - Su, min=1e-300)
+        drh = rh * (du - rh)
+    else:
+        rh = fu / torch.clamp(Fu, min=1e-300)
+        drh = rh * (-zu - rh)
+    g = torch.where(left, rh / sig, g)
+    h = torch.where(left, -drh / s2, h)
+    # interval
+    D = torch.clamp(Sl - Su, min=1e-300)
+    df = fu - fl
+    interval = ~(unc | right | left)
+    g = torch.where(interval, df / (sig * D), g)
+    h = torch.where(interval,
+                    (df * df / (D * D) - (fu * du - fl * dl) / D) / s2, h)
+    return _weighted_pair(g, torch.clamp(h, min=1e-6), weight)
+
+
+def aft_nll_rows(margin, label, dist, sigma):
+    """Per-row aft-nloglik term, float64."""
+    import math
+
+    sig = float(sigma)
+    lo, zl, zu, unc, right, left = _aft_rows(margin, label, sig)
+    fl, _, _, Fl = _aft_terms(dist, zl)
+    Fu = _aft_terms(dist, zu)[3]
+    D = torch.where(right, 1.0 - Fl, torch.where(left, Fu, Fu - Fl))
+    return torch.where(
+        unc, -torch.log(torch.clamp(fl, min=1e-12)) + math.log(sig) + lo,
+        -torch.log(torch.clamp(D, min=1e-12)))
+
+
+def eval_aft(margin, label, weight, dist, sigma):
+    nll = aft_nll_rows(margin, label, dist, sigma)
+    w = (torch.ones_like(nll) if weight is None
+         else weight.float().double())
+    return torch.stack([(w * nll).sum(), w.sum()])
+
+
+def cox_layout(label):
+    """What survival:cox needs of the labels alone, on label's device: the
+    stable descending-time order (int32), for every sorted position the
+    first and last position of its tie block (int32), and the event flag in
+    sorted order (uint8)."""
+    from collections import namedtuple
+
+    lay = namedtuple("CoxLayout", "order first last event")
+    n = label.numel()
+    dev = label.device
+    if n == 0:
+        e = torch.zeros(0, dtype=torch.int32, device=dev)
+        return lay(e, e, e, e.to(torch.uint8))
+    if n > 2 ** 31 - 1:
+        raise ValueError("survival:cox layout holds at most 2^31 - 1 rows")
+    lab = label.float()
+    order = torch.argsort(-lab.abs(), stable=True)
+    t_s = lab.abs()[order]
+    pos = torch.arange(n, dtype=torch.int32, device=dev)
+    # The blocks are those of ``Cox.gradients`` as it stands, so that the
+    # GPU route computes what the torch route does: its block id is the
+    # inclusive count of positions whose successor has another time, which
+    # opens a block AT the last row of a run of equal times, not after it.
+    # With distinct times every row is its own block either way.
+    change = torch.ones(n, dtype=torch.bool, device=dev)
+    change[:-1] = t_s[:-1] != t_s[1:]
+    start = change.clone()
+    start[0] = True
+    end = torch.ones(n, dtype=torch.bool, device=dev)
+    end[:-1] = start[1:]
+    first = torch.cummax(torch.where(start, pos, 0), 0).values
+    last = torch.cummin(
+        torch.where(end, pos, n - 1).flip(0), 0).values.flip(0)
+    return lay(order.to(torch.int32).contiguous(),
+               first.to(torch.int32).contiguous(),
+               last.to(torch.int32).contiguous(),
+               (lab > 0)[order].to(torch.uint8).contiguous())
+
+
+def cox_terms(margin, layout):
+    """Float64 (m - shift, eta, C, A, B, ev) in sorted order: the pieces of
+    the Cox contract, shared by the forms below and by the tests' bounds."""
+    m32 = margin.float()
+    m = m32.double() - m32.max().double()
+    o = layout.order.long()
+    m_s = m[o]
+    eta = torch.exp(m_s)
+    ev = layout.event.double()
+    C = torch.cumsum(eta, 0)
+    R = torch.clamp(C[layout.last.long()], min=1e-300)
+    first = layout.first.long()
+    A = torch.flip(torch.cumsum(torch.flip(ev / R, [0]), 0), [0])[first]
+    B = torch.flip(torch.cumsum(torch.flip(ev / (R * R), [0]), 0), [0])[first]
+    return m_s, eta, C, A, B, ev
+
+
+def cox_grad(margin, layout, weight=None):
+    if margin.numel() == 0:
+        return torch.zeros(0, 2), torch.zeros(2)
+    _, eta, _, A, B, ev = cox_terms(margin, layout)
+    o = layout.order.long()
+    g = torch.empty_like(eta)
+    h = torch.empty_like(eta)
+    g[o] = -ev + eta * A
+    h[o] = torch.clamp(eta * A - eta * eta * B, min=1e-6)
+    return _weighted_pair(g, h, weight)
+
+
+def eval_cox(margin, layout):
+    if margin.numel() == 0:
+        return torch.zeros(2, dtype=torch.float64)
+    m_s, _, C, _, _, ev = cox_terms(margin, layout)
+    e = ev > 0
+    ll = (m_s[e] - torch.log(torch.clamp(C[e], min=1e-300))).sum()
+    return torch.stack([-ll, ev.sum()])

@@ -405,6 +405,73 @@ def eval_multiclass(margin, label, weight=None, chunk=0, rows=0):
         *_softmax_args(margin, label, weight), int(chunk), int(rows))
 
 
+COX_TILE_ROWS = 2048  # checked against the extension's own constant
+_AFT_DIST = {"normal": 0, "logistic": 1, "extreme": 2}
+_survival_ext = None
+
+
+def _load_survival():
+    """The survival kernels' module (csrc/survival); required like
+    ``_hip_ops``."""
+    global _survival_ext
+    if _survival_ext is None:
+        _load()  # same build; raises the build hint if nothing is built
+        import importlib
+
+        _survival_ext = importlib.import_module(
+            "xgboost_ray_amd._hip_survival_ops")
+        assert _survival_ext.COX_TILE_ROWS == COX_TILE_ROWS
+    return _survival_ext
+
+
+def _f32(t):
+    return t.contiguous().float()
+
+
+def _f32_or_empty(weight, like):
+    if weight is None:
+        return torch.zeros(0, dtype=torch.float32, device=like.device)
+    return _f32(weight)
+
+
+def _aft_args(margin, label, weight, dist, sigma):
+    if dist not in _AFT_DIST:
+        raise ValueError(f"unknown AFT distribution {dist!r}")
+    return (_f32(margin), _f32(label), _f32_or_empty(weight, margin),
+            _AFT_DIST[dist], float(sigma))
+
+
+def aft_grad(margin, label, weight, dist, sigma):
+    return tuple(_load_survival().aft_grad(
+        *_aft_args(margin, label, weight, dist, sigma)))
+
+
+def eval_aft(margin, label, weight, dist, sigma):
+    return _load_survival().eval_aft(
+        *_aft_args(margin, label, weight, dist, sigma))
+
+
+def cox_layout(label):
+    from xgboost_ray_amd.ops import cpu
+
+    return cpu.cox_layout(label)  # torch, once per label tensor
+
+
+def cox_grad(margin, layout, weight=None):
+    if margin.numel() == 0:
+        z = torch.zeros(0, 2, dtype=torch.float32, device=margin.device)
+        return z, z.new_zeros(2)
+    return tuple(_load_survival().cox_grad(
+        _f32(margin), layout.order, layout.first, layout.last, layout.event,
+        _f32_or_empty(weight, margin)))
+
+
+def eval_cox(margin, layout):
+    if margin.numel() == 0:
+        return torch.zeros(2, dtype=torch.float64, device=margin.device)
+    return _load_survival().eval_cox(_f32(margin), layout.order, layout.event)
+
+
 def update_margins(margin, ridx, starts, counts, leaf_values,
                    ridx_b=None, parity=None):
     # starts/counts/leaf_values stay on the HOST: the extension stages

@@ -734,7 +734,125 @@ def bench_survival(sizes=(1_000_000, 10_000_000),
     switches(True)
 
 
+def bench_pointwise(n=11_000_000, train_shape=(2_000_000, 28), K=3):
+    """The HIP pointwise regression kernels against the torch routes they
+    replace, on the same tensors in one process, windows alternating,
+    unweighted and weighted. The torch gradient lines include the two
+    ``abs().max()`` that ``_quantize`` then needs. ``pointwise train`` runs
+    the end-to-end rounds alone."""
+    from xgboost_ray_amd.engine import objectives as O
+    from xgboost_ray_amd.engine.metrics import get_metric
+    from xgboost_ray_amd.engine.trainer import BoostingEngine, EvalPack
+
+    dev = torch.device("cuda")
+
+    def show(name, t):
+        print(f"  {name:46s} {t[0]:9.3f} ms  [{t[1]:.3f}, {t[2]:.3f}]"
+              f"{'  outside' if len(t) > 3 and t[3] else ''}", flush=True)
+
+    def switches(on):
+        for name in ("RXGB_FUSED_GRAD", "RXGB_FUSED_EVAL"):
+            if on:
+                _os.environ.pop(name, None)
+            else:
+                _os.environ[name] = "0"
+
+    def pair(name, fn):
+        def route(on):
+            def run():
+                switches(on)
+                fn()
+            return run
+        hip, tor = _spread_alt([route(True), route(False)])
+        # the hip route earns its default only outside the torch spread
+        show(f"{name} [hip]", hip + (hip[0] < tor[1] or hip[0] > tor[2],))
+        show(f"{name} [torch]", tor)
+        switches(True)
+
+    def grad(obj, margin, label, weight):
+        def run():
+            gp = obj.gradients(margin, label, weight)
+            if (getattr(gp, "_rxgb_absmax", None) is None
+                    and getattr(gp, "_rxgb_absmax_cls", None) is None):
+                gp[..., 0].abs().amax(0), gp[..., 1].abs().amax(0)
+        return run
+
+    if _sys.argv[2:3] != ["train"]:
+        gen = torch.Generator(device=dev).manual_seed(7)
+        margin = torch.randn(n, device=dev, generator=gen)
+        margin_k = torch.randn(n, K, device=dev, generator=gen)
+        pos = torch.rand(n, device=dev, generator=gen) * 3 + 0.2
+        labels = {"count:poisson": torch.floor(2 * pos),
+                  "binary:hinge": (pos > 1.5).float()}
+        wts = torch.rand(n, device=dev, generator=gen) * 3 + 0.25
+        alphas = [0.1, 0.5, 0.9][:K]
+        for what, w in (("unweighted", None), ("weighted", wts)):
+            print(f"pointwise gradients, {n} rows, {what}")
+            for name in ("reg:absoluteerror", "count:poisson", "reg:gamma",
+                         "reg:tweedie", "reg:squaredlogerror",
+                         "reg:pseudohubererror", "binary:hinge"):
+                obj = O.get_objective(name)
+                pair(name, grad(obj, margin, labels.get(name, pos), w))
+            pair("reg:quantileerror K=1",
+                 grad(O.QuantileError(alphas[:1]), margin, pos, w))
+            pair(f"reg:quantileerror K={K}",
+                 grad(O.QuantileError(alphas), margin_k, pos, w))
+            print(f"pointwise metrics, {n} rows, {what}")
+            for metric, name in (("rmse", "reg:squarederror"),
+                                 ("rmse", "binary:logistic"),
+                                 ("mae", "reg:absoluteerror"),
+                                 ("mape", "reg:gamma"),
+                                 ("rmsle", "reg:squaredlogerror"),
+                                 ("mphe", "reg:pseudohubererror"),
+                                 ("poisson-nloglik", "count:poisson"),
+                                 ("gamma-nloglik", "reg:gamma"),
+                                 ("tweedie-nloglik@1.5", "reg:tweedie")):
+                obj, m = O.get_objective(name), get_metric(metric)
+                y = labels.get(name, pos)
+                pair(f"{metric} ({obj.eval_transform})",
+                     lambda: m.local_stats(margin, y, w, None, obj))
+            for a, mk in ((alphas[:1], margin), (alphas, margin_k)):
+                obj, m = O.QuantileError(a), get_metric("quantile")
+                pair(f"quantile K={len(a)}",
+                     lambda: m.local_stats(mk, pos, w, None, obj))
+        del margin, margin_k, wts, labels, pos
+
+    n, F = train_shape
+    gen = torch.Generator(device=dev).manual_seed(9)
+    X = torch.randn(n, F, device=dev, generator=gen)
+    y = torch.exp(0.7 * X[:, 0] + 0.3 * torch.randn(n, device=dev,
+                                                    generator=gen))
+    dm = BinnedMatrix.build(X, label=y, max_bin=256)
+    del X
+    for objective, extra in (("reg:tweedie", {}),
+                             ("reg:quantileerror", {"quantile_alpha": 0.5})):
+        for with_eval in (False, True):
+            print(f"{objective} round, {n} x {F}, depth 8, "
+                  f"{'default metric every round' if with_eval else 'no eval'}"
+                  f"; 10 rounds after 2 of warm-up")
+            for run in range(2):
+                for on in (True, False):
+                    switches(on)
+                    eng = BoostingEngine(
+                        {"objective": objective, "max_depth": 8,
+                         "tree_method": "gpu_hist", **extra}, dm)
+                    for it in range(12):
+                        if it == 2:
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                        eng.update()
+                        if with_eval:
+                            eng.eval_sets([EvalPack(name="train", X=None)])
+                    torch.cuda.synchronize()
+                    ms = (time.perf_counter() - t0) / 10 * 1e3
+                    print(f"  run {run} [{'hip' if on else 'torch'}] "
+                          f"{ms:9.3f} ms/round", flush=True)
+    switches(True)
+
+
 def main():
+    if _sys.argv[1:2] == ["pointwise"]:
+        return bench_pointwise()
     if _sys.argv[1:2] == ["survival"]:
         return bench_survival()
     if _sys.argv[1:2] == ["softmax"]:

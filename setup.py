@@ -88,6 +88,21 @@ if "--cpu-only" not in sys.argv:
                                  "-Xclang", "-packed-fp32-ops"],
                     },
                 ),
+                # The pointwise regression kernels, a module of their own
+                # with the same flags.
+                cpp_extension.CUDAExtension(
+                    name="xgboost_ray_amd._hip_pointwise_ops",
+                    sources=[os.path.join(src_dir, "pointwise",
+                                          "pointwise_ops.hip")],
+                    extra_compile_args={
+                        "cxx": ["-O3", "-std=c++17"],
+                        # -ffp-contract=off: the float32 gradients are the
+                        # bits of torch's eager chain, one rounding per op
+                        "nvcc": ["-O3", "-std=c++17", "-ffp-contract=off",
+                                 "-Xclang", "-target-feature",
+                                 "-Xclang", "-packed-fp32-ops"],
+                    },
+                ),
             ]
             cmdclass = {"build_ext": cpp_extension.BuildExtension}
     except Exception as e:  # pragma: no cover

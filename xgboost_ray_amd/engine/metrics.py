@@ -17,16 +17,37 @@ from xgboost_ray_amd.engine.objectives import rank_hip_layout, sigmoid_sizeinv
 _AUC_BINS = 16384
 
 
-def _fused_eval_ok(margin):
+def _fused_eval_ok(margin, max_dim=1):
     """GPU fused metric kernels: one pass instead of 4-6 f64 torch
-    kernels over the shard (RXGB_FUSED_EVAL=0 disables)."""
+    kernels over the shard (RXGB_FUSED_EVAL=0 disables). ``max_dim=2``
+    admits the [n, K] margin of a multi-target quantile model."""
     import os
 
     return (
         margin.is_cuda
-        and margin.dim() == 1
+        and 1 <= margin.dim() <= max_dim
         and os.environ.get("RXGB_FUSED_EVAL") != "0"
     )
+
+
+def _fused_pointwise(margin, label, weight, obj, kind, param=0.0,
+                     on_pred=True):
+    """``ops.eval_pointwise`` sums f64 [sum w * loss, sum w] when the margin
+    is a float32 GPU vector with a label vector of its length, else None.
+    ``on_pred``: the metric is defined on predictions, so the objective's
+    ``eval_transform`` stands in for ``_eval_pred``; an objective without a
+    named transform keeps the torch metric."""
+    transform = "identity"
+    if on_pred and obj is not None:
+        transform = getattr(obj, "eval_transform", None)
+    if (transform is None or not _fused_eval_ok(margin)
+            or margin.dtype != torch.float32
+            or label.dtype != torch.float32
+            or label.shape != margin.shape):
+        return None
+    from xgboost_ray_amd import ops
+
+    return ops.eval_pointwise(margin, label, weight, kind, transform, param)
 
 
 class Metric:
@@ -67,6 +88,9 @@ class RMSE(Metric):
     name = "rmse"
 
     def local_stats(self, margin, label, weight, qid, obj):
+        fused = _fused_pointwise(margin, label, weight, obj, "se")
+        if fused is not None:
+            return fused
         pred = _eval_pred(margin, obj)
         w = _w(label, weight)
         se = (w * (pred - label.double()) ** 2).sum()
@@ -80,6 +104,9 @@ class MAE(Metric):
     name = "mae"
 
     def local_stats(self, margin, label, weight, qid, obj):
+        fused = _fused_pointwise(margin, label, weight, obj, "ae")
+        if fused is not None:
+            return fused
         w = _w(label, weight)
         pred = _eval_pred(margin, obj)
         return torch.stack(
@@ -352,6 +379,10 @@ class PoissonNLogLik(Metric):
     higher_better = False
 
     def local_stats(self, margin, label, weight, qid, obj):
+        fused = _fused_pointwise(margin, label, weight, obj, "poisson",
+                                 on_pred=False)
+        if fused is not None:
+            return fused
         mu = torch.exp(margin.double()).clamp(min=1e-16)
         y = label.double()
         nll = mu - y * torch.log(mu) + torch.lgamma(y + 1.0)
@@ -367,6 +398,10 @@ class GammaNLogLik(Metric):
     higher_better = False
 
     def local_stats(self, margin, label, weight, qid, obj):
+        fused = _fused_pointwise(margin, label, weight, obj, "gamma",
+                                 on_pred=False)
+        if fused is not None:
+            return fused
         mu = torch.exp(margin.double()).clamp(min=1e-16)
         y = label.double()
         nll = y / mu + torch.log(mu)
@@ -385,6 +420,10 @@ class TweedieNLogLik(Metric):
         self.name = f"tweedie-nloglik@{self.rho}"
 
     def local_stats(self, margin, label, weight, qid, obj):
+        fused = _fused_pointwise(margin, label, weight, obj, "tweedie",
+                                 self.rho, on_pred=False)
+        if fused is not None:
+            return fused
         m = margin.double()
         y = label.double()
         r = self.rho
@@ -403,6 +442,9 @@ class RMSLE(Metric):
     higher_better = False
 
     def local_stats(self, margin, label, weight, qid, obj):
+        fused = _fused_pointwise(margin, label, weight, obj, "sle")
+        if fused is not None:
+            return fused
         p = torch.clamp(_eval_pred(margin, obj), min=-1.0 + 1e-6)
         d = torch.log1p(p) - torch.log1p(label.double())
         w = _w(label, weight)
@@ -479,6 +521,9 @@ class MAPE(Metric):
     higher_better = False
 
     def local_stats(self, margin, label, weight, qid, obj):
+        fused = _fused_pointwise(margin, label, weight, obj, "ape")
+        if fused is not None:
+            return fused
         pred = _eval_pred(margin, obj)
         y = label.double()
         w = _w(label, weight)
@@ -496,6 +541,10 @@ class MPHE(Metric):
     higher_better = False
 
     def local_stats(self, margin, label, weight, qid, obj):
+        fused = _fused_pointwise(margin, label, weight, obj, "mphe",
+                                 on_pred=False)
+        if fused is not None:
+            return fused
         r = (margin - label).double()
         loss = torch.sqrt(1.0 + r * r) - 1.0
         w = _w(label, weight)
@@ -519,6 +568,15 @@ class Quantile(Metric):
                 "eval_metric 'quantile' needs objective reg:quantileerror "
                 "with quantile_alpha"
             )
+        if (_fused_eval_ok(margin, max_dim=2)
+                and margin.dtype == torch.float32
+                and label.dtype == torch.float32 and label.dim() == 1
+                and margin.numel() == label.numel() * len(alphas)):
+            from xgboost_ray_amd import ops
+
+            if len(alphas) <= ops.QUANTILE_MAX_TARGETS:
+                return ops.eval_pointwise(margin, label, weight, "pinball",
+                                          param=alphas)
         pred = margin.double().reshape(margin.shape[0], -1)
         a = torch.tensor(alphas, dtype=torch.float64, device=margin.device)
         d = label.double().unsqueeze(1) - pred

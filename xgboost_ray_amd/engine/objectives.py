@@ -46,6 +46,11 @@ class Objective:
     name = "base"
     n_class = 0
     default_metric = "rmse"
+    # what ``transform_prediction`` does, by name: "identity", "exp" or
+    # "sigmoid" let ``ops.eval_pointwise`` apply it in its own pass; None
+    # (anything else) keeps a prediction metric on torch
+    eval_transform = "identity"
+    last_route = None
 
     def prob_to_margin(self, base_score: float) -> float:
         return base_score
@@ -78,6 +83,26 @@ class Objective:
             h = h * weight
         return torch.stack([g, h], dim=-1)
 
+    def _pointwise_hip(self, margin, label, weight, kind, param=0.0):
+        """The pairs from ``ops.pointwise_grad`` (one HIP pass, the bytes of
+        the torch composition, maxima as ``_rxgb_absmax``) when the margin
+        is a float32 GPU vector and RXGB_FUSED_GRAD is not 0, else None.
+        ``last_route`` names the route the caller then takes."""
+        import os
+
+        if not (margin.is_cuda and margin.dim() == 1
+                and margin.dtype == torch.float32
+                and label.dtype == torch.float32 and label.dim() == 1
+                and os.environ.get("RXGB_FUSED_GRAD") != "0"):
+            self.last_route = "torch"
+            return None
+        from xgboost_ray_amd import ops
+
+        gp, mx = ops.pointwise_grad(margin, label, weight, kind, param)
+        gp._rxgb_absmax = mx  # consumed by _quantize
+        self.last_route = "hip"
+        return gp
+
 
 class SquaredError(Objective):
     name = "reg:squarederror"
@@ -102,6 +127,9 @@ class AbsoluteError(Objective):
     default_metric = "mae"
 
     def gradients(self, margin, label, weight=None, qid=None):
+        gp = self._pointwise_hip(margin, label, weight, "absoluteerror")
+        if gp is not None:
+            return gp
         g = torch.sign(margin - label)
         h = torch.ones_like(margin)
         return self._apply_weight(g, h, weight)
@@ -146,6 +174,29 @@ class QuantileError(Objective):
         return self.alphas[output_index]
 
     def gradients(self, margin, label, weight=None, qid=None):
+        """A float32 GPU margin, [n] or [n, K] with K up to
+        ``ops.QUANTILE_MAX_TARGETS``, takes ``ops.quantile_grad`` (one HIP
+        pass, target-major storage, the bytes of the composition below,
+        maxima as ``_rxgb_absmax`` or per target as ``_rxgb_absmax_cls``);
+        the torch composition serves everything else and RXGB_FUSED_GRAD=0.
+        ``last_route`` names the one that ran."""
+        import os
+
+        from xgboost_ray_amd import ops
+
+        if (margin.is_cuda and margin.dtype == torch.float32
+                and label.dtype == torch.float32 and label.dim() == 1
+                and margin.dim() in (1, 2) and margin.is_contiguous()
+                and self.n_target <= ops.QUANTILE_MAX_TARGETS
+                and os.environ.get("RXGB_FUSED_GRAD") != "0"):
+            gp, mx = ops.quantile_grad(margin, label, weight, self.alphas)
+            if margin.dim() == 1:
+                gp._rxgb_absmax = mx  # consumed by _quantize
+            else:
+                gp._rxgb_absmax_cls = mx  # split per target by the engine
+            self.last_route = "hip"
+            return gp
+        self.last_route = "torch"
         a = torch.tensor(self.alphas, dtype=margin.dtype,
                          device=margin.device)
         if margin.dim() == 1:
@@ -167,6 +218,7 @@ class Logistic(Objective):
 
     name = "binary:logistic"
     default_metric = "logloss"
+    eval_transform = "sigmoid"
 
     def __init__(self, scale_pos_weight: float = 1.0):
         self.scale_pos_weight = float(scale_pos_weight)
@@ -209,6 +261,7 @@ class LogisticRaw(Logistic):
 
     name = "binary:logitraw"
     default_metric = "logloss"
+    eval_transform = "identity"
 
     def transform_prediction(self, margin):
         return margin
@@ -267,6 +320,7 @@ class SoftmaxBase(Objective):
 class SoftmaxClass(SoftmaxBase):
     name = "multi:softmax"
     default_metric = "merror"
+    eval_transform = None
 
     def transform_prediction(self, margin):
         return margin.argmax(dim=1).to(torch.float32)
@@ -275,6 +329,7 @@ class SoftmaxClass(SoftmaxBase):
 class SoftProb(SoftmaxBase):
     name = "multi:softprob"
     default_metric = "mlogloss"
+    eval_transform = None
 
     def transform_prediction(self, margin):
         return torch.softmax(margin, dim=1)
@@ -610,6 +665,7 @@ class CustomObjective(Objective):
 
     name = "custom"
     default_metric = "rmse"
+    eval_transform = None
 
     def __init__(self, fn, n_class=0):
         self.fn = fn
@@ -647,11 +703,15 @@ class Poisson(Objective):
 
     name = "count:poisson"
     default_metric = "poisson-nloglik"
+    eval_transform = "exp"
 
     def prob_to_margin(self, base_score):
         return math.log(max(base_score, _EPS))
 
     def gradients(self, margin, label, weight=None, qid=None):
+        gp = self._pointwise_hip(margin, label, weight, "poisson")
+        if gp is not None:
+            return gp
         mu = elemwise_sizeinv(torch.exp, margin)
         g = mu - label
         h = mu
@@ -670,11 +730,15 @@ class Gamma(Objective):
 
     name = "reg:gamma"
     default_metric = "gamma-nloglik"
+    eval_transform = "exp"
 
     def prob_to_margin(self, base_score):
         return math.log(max(base_score, _EPS))
 
     def gradients(self, margin, label, weight=None, qid=None):
+        gp = self._pointwise_hip(margin, label, weight, "gamma")
+        if gp is not None:
+            return gp
         ratio = label * elemwise_sizeinv(torch.exp, -margin)
         g = 1.0 - ratio
         h = ratio
@@ -693,6 +757,7 @@ class Tweedie(Objective):
 
     name = "reg:tweedie"
     default_metric = "tweedie-nloglik"
+    eval_transform = "exp"
 
     def __init__(self, rho: float = 1.5):
         self.rho = float(rho)
@@ -702,6 +767,9 @@ class Tweedie(Objective):
         return math.log(max(base_score, _EPS))
 
     def gradients(self, margin, label, weight=None, qid=None):
+        gp = self._pointwise_hip(margin, label, weight, "tweedie", self.rho)
+        if gp is not None:
+            return gp
         r = self.rho
         a = elemwise_sizeinv(torch.exp, (1.0 - r) * margin)
         b = elemwise_sizeinv(torch.exp, (2.0 - r) * margin)
@@ -724,6 +792,9 @@ class SquaredLogError(Objective):
     default_metric = "rmsle"
 
     def gradients(self, margin, label, weight=None, qid=None):
+        gp = self._pointwise_hip(margin, label, weight, "squaredlogerror")
+        if gp is not None:
+            return gp
         p1 = torch.clamp(margin + 1.0, min=1e-6)
         d = elemwise_sizeinv(torch.log, p1) - elemwise_sizeinv(
             torch.log, torch.clamp(label + 1.0, min=1e-6)
@@ -760,6 +831,7 @@ class AFT(Objective):
 
     name = "survival:aft"
     default_metric = "aft-nloglik"
+    eval_transform = "exp"
 
     def __init__(self, dist: str = "normal", sigma: float = 1.0):
         self.dist = dist
@@ -964,6 +1036,7 @@ class Cox(Objective):
 
     name = "survival:cox"
     default_metric = "cox-nloglik"
+    eval_transform = "exp"
     last_route = None
 
     def gradients(self, margin, label, weight=None, qid=None):
@@ -1053,6 +1126,9 @@ class PseudoHuber(Objective):
         self.delta = float(delta)
 
     def gradients(self, margin, label, weight=None, qid=None):
+        gp = self._pointwise_hip(margin, label, weight, "pseudohuber", self.delta)
+        if gp is not None:
+            return gp
         r = margin - label
         z = 1.0 + (r / self.delta) ** 2
         sq = torch.sqrt(z)
@@ -1066,8 +1142,12 @@ class Hinge(Objective):
 
     name = "binary:hinge"
     default_metric = "error"
+    eval_transform = None  # a step
 
     def gradients(self, margin, label, weight=None, qid=None):
+        gp = self._pointwise_hip(margin, label, weight, "hinge")
+        if gp is not None:
+            return gp
         y = 2.0 * label - 1.0  # {0,1} -> {-1,+1}
         active = margin * y < 1.0
         g = torch.where(active, -y, torch.zeros_like(margin))

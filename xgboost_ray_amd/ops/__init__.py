@@ -674,3 +674,67 @@ def eval_cox(margin, layout):
     rows, m - shift - log(max(C_s, 1e-300)) (C_s itself, not tie-adjusted,
     as ``CoxNLogLik`` has it)."""
     return _impl(margin).eval_cox(margin, layout)
+
+
+# Targets that the GPU quantile kernels serve (asserted equal to the
+# module's on load); a wider reg:quantileerror stays on torch
+QUANTILE_MAX_TARGETS = _cpu.QUANTILE_MAX_TARGETS
+POINTWISE_GRAD_KINDS = _cpu.POINTWISE_GRAD_KINDS
+POINTWISE_EVAL_KINDS = _cpu.POINTWISE_EVAL_KINDS
+
+
+def pointwise_grad(margin, label, weight, kind, param=0.0, **kw):
+    """Gradient pairs of a pointwise regression objective and their maxima,
+    one pass.
+
+    margin, label: f32 [n]; weight: f32 [n] or None; kind: one of
+    POINTWISE_GRAD_KINDS; param: rho for "tweedie", huber_slope for
+    "pseudohuber". Returns (gpair [n, 2], absmax [2]).
+
+    On the GPU the result is float32 and holds the bytes of the objective
+    class's torch composition on the same tensors: the same float32
+    operation order with one rounding per torch op, the same clamps and
+    constants, Python scalars rounded to float32 where torch rounds them, a
+    division by a Python scalar as the product with its float32 reciprocal,
+    ``** 2`` as a product, and the weight's two float32 multiplies last. NaN
+    goes where torch sends it: through exp, log and sqrt it stays NaN,
+    ``sign`` turns it into 0, hinge's comparison is false so the row gets
+    (0, 1e-16). absmax == gpair.abs().amax(0) bitwise, NaN kept. A margin
+    view that starts off a 16-byte boundary takes scalar loads, not a copy.
+    ``max_blocks`` caps the grid (tests force grid-stride turns with it).
+
+    On CPU tensors this is ``ops.cpu.pointwise_grad``: the numpy float64
+    form, returned as float64, the high-precision reference."""
+    return _impl(margin).pointwise_grad(margin, label, weight, kind, param,
+                                        **kw)
+
+
+def quantile_grad(margin, label, weight, alphas, **kw):
+    """reg:quantileerror pairs and maxima: g = 1 - a_k where m - y >= 0,
+    else -a_k (so for NaN), with a_k rounded to float32 first; h = 1; then
+    the weight in float32. margin f32 [n] gives (gpair [n, 2], absmax [2]).
+    margin f32 [n, K] row-major, K = len(alphas) <= QUANTILE_MAX_TARGETS,
+    gives gpair [n, K, 2] stored target-major ([K, n, 2], permuted), so
+    every ``gpair[:, k, :]`` is contiguous, and absmax [K, 2]. On the GPU
+    the bytes equal ``QuantileError.gradients``'s torch composition."""
+    return _impl(margin).quantile_grad(margin, label, weight, alphas, **kw)
+
+
+def eval_pointwise(margin, label, weight, kind, transform="identity",
+                   param=0.0, **kw):
+    """f64 [2] = [sum w * loss, sum w] of a regression metric (w = 1 without
+    weights), per row in float64 from the float32 inputs.
+
+    kind: one of POINTWISE_EVAL_KINDS, the loss of rmse, mae, mape, rmsle,
+    mphe, poisson-nloglik, gamma-nloglik, tweedie-nloglik (param = rho) and
+    quantile (kind "pinball": margin [n, K] or [n], param = the alpha list,
+    loss = the mean over the row's targets), with the clamps of the metric
+    classes. transform: "identity", "exp" or "sigmoid", the objective's
+    prediction transform for the kinds defined on predictions (se, ae, ape,
+    sle); the others take the margin itself. On the GPU the sums run in a
+    fixed order (a thread's rows in order, a butterfly inside a wave, wave
+    order, then a sum over the workgroups' partials) with no atomics: equal
+    inputs give equal bytes. ``ops.cpu.eval_pointwise`` sums with
+    ``math.fsum`` and is the reference."""
+    return _impl(margin).eval_pointwise(margin, label, weight, kind,
+                                        transform, param, **kw)

@@ -1238,3 +1238,168 @@ def eval_cox(margin, layout):
     e = ev > 0
     ll = (m_s[e] - torch.log(torch.clamp(C[e], min=1e-300))).sum()
     return torch.stack([-ll, ev.sum()])
+
+
+# --- pointwise regression (contract: docs/parity.md "Regression on the
+# device") -------------------------------------------------------------------
+# numpy float64 forms written from the formulae, not from the objective and
+# metric classes; tests/test_pointwise_ops_cpu.py pins them to those classes.
+
+POINTWISE_GRAD_KINDS = ("absoluteerror", "poisson", "gamma", "tweedie",
+                        "squaredlogerror", "pseudohuber", "hinge")
+POINTWISE_EVAL_KINDS = ("se", "ae", "ape", "sle", "mphe", "poisson", "gamma",
+                        "tweedie", "pinball")
+POINTWISE_TRANSFORMS = ("identity", "exp", "sigmoid")
+QUANTILE_MAX_TARGETS = 16  # targets the GPU quantile kernels serve
+
+
+def _f64(a):
+    import numpy as np
+
+    return np.asarray(_as_numpy(a), np.float32).astype(np.float64)
+
+
+def pointwise_terms(margin, label, kind, param=0.0):
+    """Float64 (g, h, scale_g, scale_h) of every row, unweighted. scale is
+    the largest addend that a float32 chain rounds on its way to the value
+    (for squaredlogerror at least 1: rounding m + 1 moves the log by an
+    absolute 2^-24); the tests' bounds are built from it."""
+    import numpy as np
+
+    m, y = _f64(margin), _f64(label)
+    one = np.ones_like(m)
+    with np.errstate(all="ignore"):
+        if kind == "absoluteerror":
+            g, h = np.sign(m - y), one
+            g = np.where(np.isnan(g), 0.0, g)  # torch.sign(NaN) is 0
+            sg, sh = one, one
+        elif kind == "poisson":
+            mu = np.exp(m)
+            g, h = mu - y, mu
+            sg, sh = np.maximum(mu, np.abs(y)), mu
+        elif kind == "gamma":
+            ratio = y * np.exp(-m)
+            g, h = 1.0 - ratio, ratio
+            sg, sh = np.maximum(1.0, np.abs(ratio)), np.abs(ratio)
+        elif kind == "tweedie":
+            rho = float(param)
+            a, b = np.exp((1.0 - rho) * m), np.exp((2.0 - rho) * m)
+            g = -y * a + b
+            h = -y * (1.0 - rho) * a + (2.0 - rho) * b
+            sg = np.maximum(np.abs(y * a), b)
+            sh = np.maximum(np.abs(y * (1.0 - rho) * a),
+                            np.abs((2.0 - rho) * b))
+        elif kind == "squaredlogerror":
+            p = np.maximum(m + 1.0, 1e-6)
+            lp, ly = np.log(p), np.log(np.maximum(y + 1.0, 1e-6))
+            d = lp - ly
+            g = d / p
+            h = np.maximum((1.0 - d) / (p * p), 1e-6)
+            sd = np.maximum(1.0, np.maximum(np.abs(lp), np.abs(ly)))
+            sg, sh = sd / p, sd / (p * p)
+        elif kind == "pseudohuber":
+            r = m - y
+            z = 1.0 + (r / float(param)) ** 2
+            sq = np.sqrt(z)
+            g, h = r / sq, np.maximum(1.0 / (z * sq), 1e-16)
+            sg, sh = np.abs(g), np.abs(h)
+        elif kind == "hinge":
+            t = 2.0 * y - 1.0
+            active = m * t < 1.0
+            g = np.where(active, -t, 0.0)
+            h = np.where(active, 1.0, 1e-16)
+            sg, sh = one, one
+        else:
+            raise ValueError(f"unknown pointwise gradient kind {kind!r}")
+    return g, h, sg, sh
+
+
+def _pair_f64(g, h, weight):
+    """(gpair f64 [..., 2], absmax f64 over the rows); NaN kept."""
+    import numpy as np
+
+    if weight is not None:
+        w = _f64(weight).reshape((-1,) + (1,) * (g.ndim - 1))
+        g, h = g * w, h * w
+    gp = np.stack([g, h], axis=-1)
+    absmax = np.abs(gp).max(axis=0) if len(gp) else np.zeros(gp.shape[1:])
+    return torch.from_numpy(gp), torch.from_numpy(absmax)
+
+
+def pointwise_grad(margin, label, weight, kind, param=0.0):
+    g, h, _, _ = pointwise_terms(margin, label, kind, param)
+    return _pair_f64(g, h, weight)
+
+
+def quantile_grad(margin, label, weight, alphas):
+    """g = 1 - a_k where m - y >= 0, else -a_k, with a_k rounded to float32
+    first; h = 1. margin [n] gives [n, 2], margin [n, K] gives [n, K, 2]."""
+    import numpy as np
+
+    m, y = _f64(margin), _f64(label)
+    a = np.asarray(list(alphas), np.float32).astype(np.float64)
+    if m.ndim == 1:
+        a = a[0]
+    else:
+        y = y[:, None]
+    with np.errstate(invalid="ignore"):
+        g = np.where(m - y >= 0, 1.0 - a, -a)  # false, so -a, for NaN
+    return _pair_f64(g, np.ones_like(m), weight)
+
+
+def pointwise_loss_rows(margin, label, kind, transform="identity", param=0.0):
+    """Per-row loss of a metric kind, float64 from the float32 inputs; for
+    pinball the mean over the row's targets (param is the alpha list)."""
+    import numpy as np
+
+    m, y = _f64(margin), _f64(label)
+    with np.errstate(all="ignore"):
+        if kind == "pinball":
+            a = np.asarray(list(param), np.float64)
+            d = y[:, None] - m.reshape(len(m), -1)
+            return np.where(d >= 0, a * d, (a - 1.0) * d).sum(axis=1) / len(a)
+        if transform == "exp":
+            pred = np.exp(m)
+        elif transform == "sigmoid":
+            pred = 1.0 / (1.0 + np.exp(-m))
+        elif transform == "identity":
+            pred = m
+        else:
+            raise ValueError(f"unknown transform {transform!r}")
+        if kind == "se":
+            return (pred - y) ** 2
+        if kind == "ae":
+            return np.abs(pred - y)
+        if kind == "ape":
+            return np.abs(pred - y) / np.maximum(np.abs(y), 1e-10)
+        if kind == "sle":
+            d = np.log1p(np.maximum(pred, -1.0 + 1e-6)) - np.log1p(y)
+            return d * d
+        if kind == "mphe":  # the metric subtracts in float32
+            r = (np.asarray(_as_numpy(margin), np.float32)
+                 - np.asarray(_as_numpy(label), np.float32)).astype(np.float64)
+            return np.sqrt(1.0 + r * r) - 1.0
+        mu = np.maximum(np.exp(m), 1e-16)
+        if kind == "poisson":
+            return mu - y * np.log(mu) + torch.lgamma(
+                torch.from_numpy(y + 1.0)).numpy()
+        if kind == "gamma":
+            return y / mu + np.log(mu)
+        if kind == "tweedie":
+            rho = float(param)
+            return (-y * np.exp((1.0 - rho) * m) / (1.0 - rho)
+                    + np.exp((2.0 - rho) * m) / (2.0 - rho))
+    raise ValueError(f"unknown pointwise metric kind {kind!r}")
+
+
+def eval_pointwise(margin, label, weight, kind, transform="identity",
+                   param=0.0):
+    """f64 [2] = [sum w * loss, sum w], both by ``math.fsum``."""
+    import math
+
+    import numpy as np
+
+    loss = pointwise_loss_rows(margin, label, kind, transform, param)
+    w = np.ones_like(loss) if weight is None else _f64(weight)
+    return torch.tensor([math.fsum(w * loss), math.fsum(w)],
+                        dtype=torch.float64)

@@ -472,6 +472,89 @@ def eval_cox(margin, layout):
     return _load_survival().eval_cox(_f32(margin), layout.order, layout.event)
 
 
+QUANTILE_MAX_TARGETS = 16  # checked against the extension's own constant
+_GRAD_KIND = {"absoluteerror": 0, "poisson": 1, "gamma": 2, "tweedie": 3,
+              "squaredlogerror": 4, "pseudohuber": 5, "hinge": 6}
+_GRAD_QUANTILE = 7
+_EVAL_KIND = {"se": 0, "ae": 1, "ape": 2, "sle": 3, "mphe": 4, "poisson": 5,
+              "gamma": 6, "tweedie": 7}
+_TRANSFORM = {"identity": 0, "exp": 1, "sigmoid": 2}
+_pointwise_ext = None
+
+
+def _load_pointwise():
+    """The pointwise regression kernels' module (csrc/pointwise); required
+    like ``_hip_ops``."""
+    global _pointwise_ext
+    if _pointwise_ext is None:
+        _load()  # same build; raises the build hint if nothing is built
+        import importlib
+
+        _pointwise_ext = importlib.import_module(
+            "xgboost_ray_amd._hip_pointwise_ops")
+        assert _pointwise_ext.MAX_TARGETS == QUANTILE_MAX_TARGETS
+    return _pointwise_ext
+
+
+def pointwise_grad(margin, label, weight, kind, param=0.0, max_blocks=0):
+    if kind not in _GRAD_KIND:
+        raise ValueError(f"unknown pointwise gradient kind {kind!r}")
+    p0 = p1 = 0.0
+    if kind == "tweedie":
+        p0, p1 = 1.0 - float(param), 2.0 - float(param)
+    elif kind == "pseudohuber":
+        # torch divides by a Python scalar as a product with its float32
+        # reciprocal
+        p0 = (1.0 / torch.tensor(float(param), dtype=torch.float32)).item()
+    return tuple(_load_pointwise().pointwise_grad(
+        _f32(margin), _f32(label), _f32_or_empty(weight, margin),
+        _GRAD_KIND[kind], p0, p1, int(max_blocks)))
+
+
+def quantile_grad(margin, label, weight, alphas, max_blocks=0):
+    a = torch.tensor(list(alphas), dtype=torch.float32)
+    hi, lo = (1.0 - a).tolist(), (-a).tolist()  # float32 values
+    ext = _load_pointwise()
+    m, y, w = _f32(margin), _f32(label), _f32_or_empty(weight, margin)
+    if m.dim() == 1:
+        return tuple(ext.pointwise_grad(m, y, w, _GRAD_QUANTILE, hi[0], lo[0],
+                                        int(max_blocks)))
+    if m.shape[1] != len(hi) or len(hi) > QUANTILE_MAX_TARGETS:
+        raise ValueError(
+            f"quantile_grad serves [n, K] margins with K = len(alphas) <= "
+            f"{QUANTILE_MAX_TARGETS}, got {tuple(m.shape)} and {len(hi)}")
+    store, absmax = ext.quantile_grad(m, y, w, hi, lo, int(max_blocks))
+    # stored target-major [K, n, 2]: every gpair[:, k, :] is contiguous
+    return store.permute(1, 0, 2), absmax
+
+
+def eval_pointwise(margin, label, weight, kind, transform="identity",
+                   param=0.0, max_blocks=0):
+    ext = _load_pointwise()
+    m, y, w = _f32(margin), _f32(label), _f32_or_empty(weight, margin)
+    if kind == "pinball":
+        alphas = [float(a) for a in param]
+        m = m.reshape(m.shape[0], -1)
+        if m.shape[1] != len(alphas) or len(alphas) > QUANTILE_MAX_TARGETS:
+            raise ValueError(
+                f"pinball serves [n, K] margins with K = len(alphas) <= "
+                f"{QUANTILE_MAX_TARGETS}, got {tuple(m.shape)} and "
+                f"{len(alphas)}")
+        s = ext.eval_pinball(m, y, w, alphas, int(max_blocks))
+        return torch.stack([s[0] / len(alphas), s[1]])
+    if kind not in _EVAL_KIND or transform not in _TRANSFORM:
+        raise ValueError(
+            f"unknown pointwise metric kind {kind!r} or transform "
+            f"{transform!r}")
+    p0 = p1 = 0.0
+    if kind == "tweedie":
+        p0, p1 = 1.0 - float(param), 2.0 - float(param)
+    if _EVAL_KIND[kind] >= _EVAL_KIND["mphe"]:
+        transform = "identity"  # defined on the margin itself
+    return ext.eval_pointwise(m, y, w, _EVAL_KIND[kind],
+                              _TRANSFORM[transform], p0, p1, int(max_blocks))
+
+
 def update_margins(margin, ridx, starts, counts, leaf_values,
                    ridx_b=None, parity=None):
     # starts/counts/leaf_values stay on the HOST: the extension stages

@@ -850,7 +850,96 @@ def bench_pointwise(n=11_000_000, train_shape=(2_000_000, 28), K=3):
     switches(True)
 
 
+def bench_sketch(shapes=((11_000_000, 28), (1_000_000, 200)),
+                 train_shape=(2_000_000, 28)):
+    """The HIP weighted sketch (tree_method="approx"): every radix pass
+    alone on the tables the real select produced, the whole
+    ``weighted_cuts`` (passes + select), the re-bin into the resident
+    matrix and the ``bins_t`` refresh; and, windows alternating in the same
+    process, sketch + re-bin against the torch ``build_cuts`` +
+    ``bin_matrix`` of the hist route on the same data. ``sketch train``
+    runs approx against hist rounds alone."""
+    from xgboost_ray_amd.engine.quantile import build_cuts
+    from xgboost_ray_amd.engine.trainer import BoostingEngine
+
+    dev = torch.device("cuda")
+
+    def show(name, t):
+        print(f"  {name:46s} {t[0]:9.3f} ms  [{t[1]:.3f}, {t[2]:.3f}]",
+              flush=True)
+
+    for n, F in (() if _sys.argv[2:3] == ["train"] else shapes):
+        print(f"sketch, {n} x {F}, max_bin 256, hessian-like int32 weights")
+        gen = torch.Generator(device=dev).manual_seed(3)
+        X = torch.randn(n, F, device=dev, generator=gen)
+        p = torch.sigmoid(torch.randn(n, device=dev, generator=gen))
+        gq = torch.stack([p, p * (1 - p) * 4], 1).mul_(2.0 ** 30).round_().to(
+            torch.int32)
+        W = gq[:, 1]
+        col_max = X.amax(0)
+        calls = []
+        real_pass = ops.sketch_pass
+        ops.sketch_pass = lambda *a: (calls.append(a), real_pass(*a))[1]
+        cuts = ops.weighted_cuts(X, W, 256, col_max)
+        ops.sketch_pass = real_pass
+        passes = 0.0
+        for a in calls:
+            out = torch.zeros_like(a[6])
+            t = _spread(lambda: real_pass(*a[:6], out))
+            show(f"pass {a[4]} ({int(a[3].sum())} slots)", t)
+            passes += t[0]
+        del out, calls
+        whole = _spread(lambda: ops.weighted_cuts(X, W, 256, col_max))
+        show("weighted_cuts (4 passes + select)", whole)
+        print(f"  {'select and glue (whole - passes)':46s} "
+              f"{whole[0] - passes:9.3f} ms")
+        bins = ops.bin_matrix(X, cuts.cuts_flat, cuts.cut_ptr)
+        bins_t = bins.t().contiguous()
+        show("re-bin (bin_matrix out=)", _spread(lambda: ops.bin_matrix(
+            X, cuts.cuts_flat, cuts.cut_ptr, out=bins)))
+        show("bins_t refresh", _spread(lambda: bins_t.copy_(bins.t())))
+
+        def hip():
+            c = ops.weighted_cuts(X, W, 256, col_max)
+            ops.bin_matrix(X, c.cuts_flat, c.cut_ptr, out=bins)
+
+        def parent():
+            c = build_cuts(X, 256)
+            ops.bin_matrix(X, c.cuts_flat, c.cut_ptr)
+
+        th, tp = _spread_alt([hip, parent], reps=3, inner=1)
+        show("sketch + re-bin [hip, weighted]", th)
+        show("build_cuts + bin_matrix [torch, unweighted]", tp)
+        del X, W, gq, bins, bins_t
+
+    n, F = train_shape
+    gen = torch.Generator(device=dev).manual_seed(9)
+    X = torch.randn(n, F, device=dev, generator=gen)
+    y = (X[:, 0] + 0.5 * X[:, 1] > 0).float()
+    dms = {"gpu_approx": BinnedMatrix.build(X, label=y, max_bin=256,
+                                            keep_raw=True),
+           "gpu_hist": BinnedMatrix.build(X, label=y, max_bin=256)}
+    print(f"binary:logistic round, {n} x {F}, depth 8; 10 rounds after 2 of "
+          f"warm-up (approx: per-depth path unless the enqueue applies)")
+    for run in range(2):
+        for tm in ("gpu_approx", "gpu_hist"):
+            eng = BoostingEngine({"objective": "binary:logistic",
+                                  "max_depth": 8, "tree_method": tm},
+                                 dms[tm])
+            for it in range(12):
+                if it == 2:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                eng.update()
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) / 10 * 1e3
+            print(f"  run {run} [{tm}, {eng.last_tree_path}] "
+                  f"{ms:9.3f} ms/round", flush=True)
+
+
 def main():
+    if _sys.argv[1:2] == ["sketch"]:
+        return bench_sketch()
     if _sys.argv[1:2] == ["pointwise"]:
         return bench_pointwise()
     if _sys.argv[1:2] == ["survival"]:

@@ -103,6 +103,17 @@ if "--cpu-only" not in sys.argv:
                                  "-Xclang", "-packed-fp32-ops"],
                     },
                 ),
+                # The weighted quantile sketch kernels (tree_method="approx"),
+                # a module of their own: integer sums only, so no float flag.
+                cpp_extension.CUDAExtension(
+                    name="xgboost_ray_amd._hip_sketch_ops",
+                    sources=[os.path.join(src_dir, "sketch",
+                                          "sketch_ops.hip")],
+                    extra_compile_args={
+                        "cxx": ["-O3", "-std=c++17"],
+                        "nvcc": ["-O3", "-std=c++17"],
+                    },
+                ),
             ]
             cmdclass = {"build_ext": cpp_extension.BuildExtension}
     except Exception as e:  # pragma: no cover

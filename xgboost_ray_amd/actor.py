@@ -146,12 +146,23 @@ class _ActorWorker:
             master_port=comm_args["master_port"],
             device=self.device,
         )
+        # approx re-sketches per tree from the fp32 features, which stay
+        # resident next to the bins (4x their size)
+        approx = (str(params.get("tree_method") or "")
+                  in ("approx", "gpu_approx")
+                  and params.get("booster") != "gblinear")
         try:
             if shard.get("streaming"):
                 if params.get("booster") == "gblinear":
                     raise ValueError(
                         "booster=gblinear is not supported with streaming "
                         "(RayDeviceQuantileDMatrix) training data"
+                    )
+                if approx:
+                    raise ValueError(
+                        "tree_method=approx is not supported with streaming "
+                        "(RayDeviceQuantileDMatrix) training data: it "
+                        "re-bins the raw features for every tree"
                     )
                 loader = shard["loader"]
 
@@ -180,7 +191,8 @@ class _ActorWorker:
                     max_bin=int(params.get("max_bin", 256)),
                     collective=coll,
                     seed=int(params.get("seed", 0) or 0),
-                    keep_raw=params.get("booster") == "gblinear",
+                    keep_raw=(params.get("booster") == "gblinear"
+                              or approx),
                 )
                 del t_x
                 if shard.get("feature_weights") is not None:

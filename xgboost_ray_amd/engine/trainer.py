@@ -27,7 +27,7 @@ from xgboost_ray_amd.booster import Booster, Tree
 from xgboost_ray_amd.engine.collective import Collective
 from xgboost_ray_amd.engine.metrics import get_metric
 from xgboost_ray_amd.engine.objectives import Objective, get_objective
-from xgboost_ray_amd.engine.quantile import BinnedMatrix
+from xgboost_ray_amd.engine.quantile import BinnedMatrix, HistogramCuts
 
 _QUANT_BITS = 30
 
@@ -392,6 +392,22 @@ class BoostingEngine:
             )
         self.feat_bins = dtrain.cuts.feat_bins().to(self.device)
         self.n_bins = dtrain.cuts.max_bins
+        # tree_method="approx": the cuts are re-sketched for every tree
+        # with the hessians as weights (_resketch); the histogram stride
+        # stays at the bin budget so no buffer shape moves between trees
+        self._approx = (
+            str(self.p.tree_method) in ("approx", "gpu_approx")
+            and self.p.booster != "gblinear"
+        )
+        if self._approx:
+            if getattr(dtrain, "raw_X", None) is None:
+                raise ValueError(
+                    "tree_method=approx needs the raw feature matrix - "
+                    "build the BinnedMatrix with keep_raw=True (streaming "
+                    "matrices are not supported for approx)"
+                )
+            self.n_bins = max(self.n_bins, min(self.p.max_bin, 255))
+            self._col_max = self._global_col_max(dtrain.raw_X)
         self.mono = None
         mc = self.p.monotone_constraints
         if mc:
@@ -477,6 +493,61 @@ class BoostingEngine:
     def _allreduce_hook(self):
         return self.coll.allreduce_ if self.coll.is_distributed else None
 
+    # -- tree_method="approx": per-tree hessian-weighted cuts -----------------
+    def _global_col_max(self, X: torch.Tensor) -> torch.Tensor:
+        """f32 [F]: the largest non-NaN value of every column over all
+        ranks, NaN for an all-missing one (once per matrix, one MAX
+        allreduce)."""
+        nan = torch.isnan(X)
+        neg_inf = torch.full_like(X[:1], float("-inf"))
+        mx = torch.where(nan, neg_inf, X).amax(0) if X.shape[0] else neg_inf[0]
+        packed = torch.stack([mx, (~nan).any(0).float()])
+        if self.coll.is_distributed:
+            self.coll.allreduce_(packed, op="max")
+        return torch.where(packed[1] > 0, packed[0],
+                           torch.full_like(packed[0], float("nan")))
+
+    def _install_cuts(self, cuts: HistogramCuts):
+        """Make ``cuts`` the training matrix's cuts: re-bin the raw features
+        into the resident bin storage, refresh its column-major copy and the
+        engine's per-feature bin counts. ``n_bins`` (the histogram stride)
+        does not move. The growers read the host copies of the cut values
+        from ``dtrain.cuts`` at the start of each tree, after this."""
+        dm = self.dtrain
+        dm.cuts = cuts
+        ops.bin_matrix(dm.raw_X, cuts.cuts_flat, cuts.cut_ptr, out=dm.bins)
+        if getattr(dm, "bins_t", None) is not None:
+            dm.bins_t.copy_(dm.bins.t())
+        self.feat_bins = cuts.feat_bins().to(self.device)
+
+    def _resketch(self, gq: torch.Tensor):
+        """One exact weighted sketch with this tree's quantized hessians as
+        row weights (int32 on a global scale, so world-consistent; every row
+        counts, sampled or not), then ``_install_cuts``."""
+        cuts = ops.weighted_cuts(
+            self.dtrain.raw_X, gq[:, 1], self.p.max_bin, self._col_max,
+            allreduce=self._allreduce_hook(),
+        )
+        self._install_cuts(cuts)
+
+    def _add_tree_margin_by_value(self, t: Tree, margin_view):
+        """Add one tree's leaf values by walking the raw features: under
+        approx the bins belong to the latest tree only, and thresholds are
+        cut values, so "x < thr" is the routing every tree was grown with."""
+        n = self.dtrain.n_rows
+        add = torch.zeros(n, dtype=torch.float32, device=self.device)
+        ops.predict_trees(
+            self.dtrain.raw_X,
+            torch.from_numpy(t.feat).to(self.device),
+            torch.from_numpy(t.thr).to(self.device),
+            torch.from_numpy(t.left).to(self.device),
+            torch.from_numpy(t.default_left).to(self.device),
+            torch.from_numpy(t.value).to(self.device),
+            torch.tensor([0, t.num_nodes], dtype=torch.int32),
+            add,
+        )
+        margin_view += add
+
     def _quantile_intercept(self) -> float:
         """Mean over alphas of the global alpha-quantile of the labels: the
         leaf select over one segment covering all rows, residual = label."""
@@ -553,6 +624,13 @@ class BoostingEngine:
         self._replay_trees_binned(model)
 
     def _replay_trees_binned(self, model: Booster):
+        if self._approx:
+            for i, t in enumerate(model.trees):
+                cls = model.tree_info[i] if i < len(model.tree_info) else 0
+                self._add_tree_margin_by_value(
+                    t, self.margin if self.n_class == 1
+                    else self.margin[:, cls])
+            return
         cuts = self.dtrain.cuts
         cut_ptr = cuts.cut_ptr.cpu().numpy()
         cuts_np = cuts.cuts_flat.cpu().numpy()
@@ -727,6 +805,8 @@ class BoostingEngine:
 
     def _add_tree_margin_raw(self, t, margin_view):
         """Add one tree's predictions via the binned matrix (exact)."""
+        if self._approx:
+            return self._add_tree_margin_by_value(t, margin_view)
         cuts = self.dtrain.cuts
         cut_ptr = cuts.cut_ptr.cpu().numpy()
         cuts_np = cuts.cuts_flat.cpu().numpy()
@@ -1031,6 +1111,9 @@ class BoostingEngine:
             _tick("mvs_sample")
         gq, scale_g, scale_h = self._quantize(gpair)
         _tick("quantize")
+        if self._approx:
+            self._resketch(gq)
+            _tick("sketch")
         self._scale_g_cur = scale_g
         self._leaf_segs = []
         self._leaf_nids = []

@@ -134,7 +134,8 @@ class _TrainingState:
 
 def _autodetect_resources(ray_params: RayParams, use_tree_method: bool):
     """GPU autodetection: gpus_per_actor = 1 when tree_method is gpu_*
-    (reference main.py:835-859)."""
+    (reference main.py:835-859). ``approx`` is detected like ``hist``: it
+    runs on the CPU unless spelled ``gpu_approx`` or given device="cuda"."""
     gpus = ray_params.gpus_per_actor
     if gpus == -1:
         gpus = 1 if use_tree_method and torch.cuda.is_available() else 0
@@ -511,13 +512,25 @@ def train(
 
     # unsupported tree methods (reference main.py:1508-1514)
     tm = (params or {}).get("tree_method", "hist") or "hist"
-    if tm in ("exact", "approx") or "colmaker" in str(
+    if tm == "exact" or "colmaker" in str(
         (params or {}).get("updater", "")
     ):
         raise ValueError(
             f"`tree_method={tm}` is not supported for distributed training: "
             "column-major / exact greedy updaters cannot be row-sharded. "
             "Use `hist` or `gpu_hist`."
+        )
+
+    # approx re-bins the resident fp32 features for every tree, which a
+    # streaming matrix never holds (the actor raises the same, as for
+    # gblinear; here it reaches the caller as a ValueError)
+    if (tm in ("approx", "gpu_approx")
+            and (params or {}).get("booster") != "gblinear"
+            and getattr(dtrain, "streaming", False)):
+        raise ValueError(
+            "tree_method=approx is not supported with streaming "
+            "(RayDeviceQuantileDMatrix) training data: it re-bins the raw "
+            "features for every tree"
         )
 
     use_gpu_params = _is_gpu_params(params)

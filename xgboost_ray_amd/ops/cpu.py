@@ -430,6 +430,82 @@ def leaf_quantile_hist(resid, weight, ridx, starts, counts, prefix, pass_idx,
     return out
 
 
+def sketch_pass(X, W, table, n_slots, pass_idx, S, out):
+    """One radix-select pass of the weighted sketch (``ops.sketch_pass``),
+    feature by feature in plain torch; int64 sums."""
+    keys = quantile_keys(X)
+    w_all = W.long().clamp(min=0)
+    flat = out.view(-1)
+    hi_shift = 32 - 8 * pass_idx
+    lo_shift = 24 - 8 * pass_idx
+    for f in range(X.shape[1]):
+        ok = ~torch.isnan(X[:, f])
+        kk, w = keys[ok, f], w_all[ok]
+        slot = torch.zeros_like(kk)
+        if pass_idx:
+            tab = table[f, : int(n_slots[f])].long()
+            if tab.numel() == 0:
+                continue
+            pfx = kk >> hi_shift
+            slot = torch.searchsorted(tab, pfx).clamp(max=tab.numel() - 1)
+            hit = tab[slot] == pfx
+            kk, w, slot = kk[hit], w[hit], slot[hit]
+        flat.index_add_(
+            0, (f * S + slot) * 256 + ((kk >> lo_shift) & 255), w)
+    return out
+
+
+def keys_to_float(keys):
+    """Inverse of ``quantile_keys``: int64 keys -> the f32 values."""
+    bits = torch.where(keys >= 0x80000000, keys ^ 0x80000000,
+                       keys ^ 0xFFFFFFFF)
+    bits = bits - ((bits >> 31) << 32)  # wrap into int32
+    return bits.to(torch.int32).view(torch.float32)
+
+
+def weighted_cuts(X, W, max_bin, col_max):
+    """Oracle of ``ops.weighted_cuts``: per feature a stable numpy sort by
+    key, an int64 cumsum and a searchsorted of the targets."""
+    import numpy as np
+
+    from xgboost_ray_amd.engine.quantile import HistogramCuts
+
+    nb = min(int(max_bin), 255)
+    Xc = X.detach().cpu().float()
+    keys = quantile_keys(Xc).numpy()
+    nan = torch.isnan(Xc).numpy()
+    w_all = np.maximum(W.detach().cpu().numpy().astype(np.int64), 0)
+    cmax = col_max.detach().cpu().numpy().astype(np.float32)
+    cuts_list = []
+    for f in range(Xc.shape[1]):
+        if np.isnan(cmax[f]):
+            cuts_list.append(np.zeros(0, np.float32))
+            continue
+        k, w = keys[~nan[:, f], f], w_all[~nan[:, f]]
+        order = np.argsort(k, kind="stable")
+        k, cw = k[order], np.cumsum(w[order])
+        Wf = int(cw[-1]) if cw.size else 0
+        vals = np.zeros(0, np.float32)
+        if Wf > 0 and nb > 1:
+            q, r = divmod(Wf, nb)
+            j = np.arange(1, nb, dtype=np.int64)
+            T = j * q + (j * r + nb - 1) // nb
+            picked = np.unique(k[np.searchsorted(cw, T, side="left")])
+            vals = keys_to_float(torch.from_numpy(picked)).numpy()
+        above = np.nextafter(cmax[f], np.float32(np.inf))
+        cuts_list.append(
+            np.unique(np.concatenate([vals, [above]]).astype(np.float32)))
+    ptr = np.zeros(len(cuts_list) + 1, dtype=np.int64)
+    ptr[1:] = np.cumsum([len(c) for c in cuts_list])
+    flat = (np.concatenate(cuts_list) if ptr[-1] > 0
+            else np.zeros(0, dtype=np.float32))
+    return HistogramCuts(
+        cuts_flat=torch.from_numpy(flat.astype(np.float32)),
+        cut_ptr=torch.from_numpy(ptr),
+        max_bins=int(max((len(c) for c in cuts_list), default=1)) or 1,
+    )
+
+
 # ---------------------------------------------------------------------------
 # Gradient-based row sampling (minimal-variance sampling)
 # ---------------------------------------------------------------------------

@@ -597,6 +597,39 @@ def leaf_quantile_hist(resid, weight, ridx, starts, counts, prefix, pass_idx,
     return out
 
 
+SKETCH_MAX_SLOTS = 254  # checked against the extension's own constant
+_sketch_ext = None
+
+
+def _load_sketch():
+    """The weighted sketch kernels' module (csrc/sketch); required like
+    ``_hip_ops``."""
+    global _sketch_ext
+    if _sketch_ext is None:
+        _load()  # same build; raises the build hint if nothing is built
+        import importlib
+
+        _sketch_ext = importlib.import_module(
+            "xgboost_ray_amd._hip_sketch_ops")
+        assert _sketch_ext.MAX_SLOTS == SKETCH_MAX_SLOTS
+    return _sketch_ext
+
+
+def sketch_pass(X, W, table, n_slots, pass_idx, S, out):
+    _load_sketch().sketch_pass(X, W, table, n_slots, pass_idx, S, out)
+    return out
+
+
+def rebin(values, cuts_flat, cut_ptr, out):
+    _load_sketch().rebin(
+        values.contiguous(),
+        cuts_flat.to(values.device),
+        cut_ptr.to(values.device),
+        out,
+    )
+    return out
+
+
 # -- gradient-based row sampling ---------------------------------------------
 def mvs_score(gpair, mx_g, mx_h):
     from xgboost_ray_amd.ops import cpu

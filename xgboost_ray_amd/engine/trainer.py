@@ -16,8 +16,11 @@ exactly reproducible (reference test_fault_tolerance.py:401-449).
 """
 
 import math
+import os
+import time
 from dataclasses import dataclass, field
-from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
+from typing import (Callable, Dict, List, NamedTuple, Optional, Sequence,
+                    Tuple, Union)
 
 import numpy as np
 import torch
@@ -179,21 +182,6 @@ class EvalPack:
     margin: Optional[torch.Tensor] = None
 
 
-@dataclass(slots=True)
-class _Node:
-    nid: int
-    depth: int
-    start: int
-    count: int
-    sum_g: int  # quantized
-    sum_h: int
-    slot: int = 0  # scan-slot in this depth's all_hist
-    parent_slot: int = 0  # parent's scan-slot in the previous depth
-    w_lower: float = -math.inf  # monotone weight bounds
-    w_upper: float = math.inf
-    path_feats: tuple = ()  # split features on the root path (sorted)
-
-
 class _TreeArrays:
     """Growable SoA node storage for depthwise growth (replaces python
     lists of per-node appends; fields are written by vectorized numpy
@@ -229,6 +217,293 @@ class _TreeArrays:
             new[: self.n] = old[: self.n]
             setattr(self, name, new)
         self.cap = cap
+
+    def record_splits(self, nids, feat, sbin, dl, gain, cover,
+                      cuts_flat, cut_ptr):
+        """Turn nodes ``nids`` into splits and append their children.
+        Returns the left child ids, in scan-slot order (matches the
+        sequential numbering the list-based builder produced)."""
+        base = self.n
+        n_split = nids.size
+        lids = base + 2 * np.arange(n_split, dtype=np.int64)
+        self.ensure(base + 2 * n_split)
+        self.feat[nids] = feat
+        # split after bin b: left iff bin <= b; bin b covers
+        # [cut[b-1], cut[b]) so "bin <= b" <=> v < cut[b] = thr.
+        self.thr[nids] = cuts_flat[cut_ptr[feat] + sbin].astype(np.float64)
+        self.split_bin[nids] = sbin
+        self.left[nids] = lids
+        self.dl[nids] = dl
+        self.gain[nids] = gain
+        self.cover[nids] = cover
+        self.parent[lids] = nids
+        self.parent[lids + 1] = nids
+        self.n = base + 2 * n_split
+        return lids
+
+    def to_tree(self) -> Tree:
+        n = self.n
+        return Tree(
+            feat=self.feat[:n].astype(np.int32),
+            thr=self.thr[:n].astype(np.float32),
+            left=self.left[:n].astype(np.int32),
+            default_left=self.dl[:n].astype(np.uint8),
+            value=self.val[:n].astype(np.float32),
+            gain=self.gain[:n].astype(np.float32),
+            cover=self.cover[:n].astype(np.float32),
+            parent=np.where(
+                self.parent[:n] < 0, 2147483647, self.parent[:n]
+            ).astype(np.int32),
+        )
+
+
+def _interleave(left, right, dtype=np.int64):
+    """[l0, r0, l1, r1, ...]: children sit next to their sibling."""
+    out = np.empty(2 * left.size, dtype)
+    out[0::2] = left
+    out[1::2] = right
+    return out
+
+
+class _Frontier:
+    """SoA frontier of depthwise growth: one numpy array per field.
+    Children are always appended as (left, right) pairs, so siblings sit
+    at positions 2i / 2i+1 and the build/derive pairing vectorizes.
+
+    ``in_build_order`` returns the same nodes in scan-slot order and sets
+    the three build fields; they are None on a frontier in child order."""
+
+    __slots__ = ("nid", "start", "count", "sumg", "sumh", "pslot", "wlo",
+                 "whi", "paths", "K", "derive_pslot", "derive_sib_pos")
+
+    def __init__(self, nid, start, count, sumg, sumh, pslot, wlo, whi,
+                 paths):
+        self.nid, self.start, self.count = nid, start, count
+        self.sumg, self.sumh = sumg, sumh  # quantized
+        self.pslot = pslot  # parent's scan slot in the previous depth
+        self.wlo, self.whi = wlo, whi  # monotone weight bounds
+        # split features on each root path (sorted tuples), or None when
+        # there are no interaction constraints
+        self.paths = paths
+        self.K = self.derive_pslot = self.derive_sib_pos = None
+
+    @classmethod
+    def root(cls, n_rows, sumg, sumh, track_paths):
+        return cls(
+            np.zeros(1, np.int64), np.zeros(1, np.int64),
+            np.array([n_rows], np.int64), np.array([sumg], np.int64),
+            np.array([sumh], np.int64), np.zeros(1, np.int64),
+            np.full(1, -np.inf), np.full(1, np.inf),
+            [()] if track_paths else None,
+        )
+
+    @property
+    def size(self):
+        return self.nid.size
+
+    def in_build_order(self, depth):
+        """Scan-slot order: per sibling pair build the globally smaller
+        child (quantized hessian sum as the size proxy - identical on
+        every rank; local counts are not), derive the sibling by
+        subtraction. Built block = the ``K`` leading slots (one
+        AllReduce, batched subtraction for the rest); derived slot K + j
+        is its parent's histogram (slot ``derive_pslot[j]`` of the previous
+        depth) minus built slot ``derive_sib_pos[j]``."""
+        if depth == 0:
+            order = np.zeros(1, np.int64)
+            K = 1
+            derive_pslot = np.zeros(0, np.int64)
+        else:
+            ia = np.arange(0, self.size, 2)
+            ib = ia + 1
+            small_is_a = self.sumh[ia] <= self.sumh[ib]
+            idx_small = np.where(small_is_a, ia, ib)
+            idx_big = np.where(small_is_a, ib, ia)
+            order = np.concatenate([idx_small, idx_big])
+            K = idx_small.size
+            derive_pslot = self.pslot[idx_big]
+        lvl = _Frontier(
+            self.nid[order], self.start[order], self.count[order],
+            self.sumg[order], self.sumh[order], self.pslot[order],
+            self.wlo[order], self.whi[order],
+            None if self.paths is None else [self.paths[i] for i in order],
+        )
+        lvl.K = K
+        lvl.derive_pslot = derive_pslot
+        lvl.derive_sib_pos = np.arange(derive_pslot.size, dtype=np.int64)
+        return lvl
+
+    def meta(self):
+        """One depth's control data as a single int64 vector: {sum_g |
+        sum_h | start | count} per scan slot, then {derive_pslot |
+        derive_sib_pos}."""
+        return np.concatenate(
+            [self.sumg, self.sumh, self.start, self.count,
+             self.derive_pslot, self.derive_sib_pos]
+        )
+
+    def bounds(self):
+        """[size, 2] float64 monotone weight bounds."""
+        return torch.from_numpy(
+            np.ascontiguousarray(np.stack([self.wlo, self.whi], axis=1))
+        )
+
+    def children(self, ok, lids, feat, lc, left_g, left_h, mono=None):
+        """The next frontier: both children of the split slots ``ok`` of
+        this level (ascending), given their left child ids, split
+        features, left row counts and left sums. ``mono``: (per-feature
+        constraint, scale_g, scale_h, lambda, alpha) or None."""
+        l_start = self.start[ok]
+        r_sumg = self.sumg[ok] - left_g
+        r_sumh = self.sumh[ok] - left_h
+        # monotone child bounds (exact op order of the scalar path)
+        wlo_p = self.wlo[ok]
+        whi_p = self.whi[ok]
+        l_wlo = r_wlo = wlo_p
+        l_whi = r_whi = whi_p
+        if mono is not None:
+            mono_np, scale_g, scale_h, lam, alpha = mono
+            cvec = mono_np[feat]
+            act = cvec != 0
+            if act.any():
+                wl = np.maximum(wlo_p, np.minimum(
+                    whi_p, _calc_weight_vec(
+                        left_g / scale_g, left_h / scale_h, lam, alpha
+                    )))
+                wr = np.maximum(wlo_p, np.minimum(
+                    whi_p, _calc_weight_vec(
+                        r_sumg / scale_g, r_sumh / scale_h, lam, alpha
+                    )))
+                mid = 0.5 * (wl + wr)
+                pos = act & (cvec > 0)
+                neg = act & (cvec < 0)
+                l_whi = np.where(pos, np.minimum(whi_p, mid), whi_p)
+                r_wlo = np.where(pos, np.maximum(wlo_p, mid), wlo_p)
+                l_wlo = np.where(neg, np.maximum(wlo_p, mid), wlo_p)
+                r_whi = np.where(neg, np.minimum(whi_p, mid), whi_p)
+        paths = None
+        if self.paths is not None:
+            paths = []
+            for k_i, f_i in zip(ok.tolist(), feat.tolist()):
+                cp = tuple(sorted(set(self.paths[k_i]) | {int(f_i)}))
+                paths += [cp, cp]
+        return _Frontier(
+            _interleave(lids, lids + 1),
+            _interleave(l_start, l_start + lc),
+            _interleave(lc, self.count[ok] - lc),
+            _interleave(left_g, r_sumg),
+            _interleave(left_h, r_sumh),
+            _interleave(ok, ok),
+            _interleave(l_wlo, r_wlo, np.float64),
+            _interleave(l_whi, r_whi, np.float64),
+            paths,
+        )
+
+
+class _Route(NamedTuple):
+    """How one depthwise tree gets its splits (decided once per tree)."""
+
+    use_fused_loop: bool  # one-sync loop with ping-pong row-id buffers
+    row_finish: bool  # margins by one row-order walk of the finished tree
+    fused_glue: bool  # derive/reduce/plan fused into scan and partition
+    tree_enq: bool  # every level enqueued by one call
+    use_depth_step: bool  # one C++ call per depth
+
+
+class _LevelSplits(NamedTuple):
+    """Best split of every scan slot of one level, as host arrays."""
+
+    gain: np.ndarray
+    feature: np.ndarray
+    bin: np.ndarray
+    default_left: np.ndarray
+    left_g: np.ndarray
+    left_h: np.ndarray
+    # left row counts of the slots that split, ascending, when the level's
+    # partition already ran on the device; None: the caller partitions
+    left_counts: Optional[np.ndarray]
+    # ping-pong row-id buffer the level was read from by that partition
+    # (0 when there is none)
+    in_buf: int
+
+
+def _decode_pull(arr, KK, lc_off, in_buf, with_counts=True):
+    """A pulled {packed [KK, 6] | left counts at ``lc_off``} int64 block."""
+    return _LevelSplits(
+        *_unpack_splits(arr[: 6 * KK].reshape(KK, 6)),
+        arr[lc_off : lc_off + KK].copy() if with_counts else None,
+        in_buf,
+    )
+
+
+class _PhaseTimer:
+    """RXGB_PROFILE_ENGINE: wall time per phase of one tree, every tick
+    behind a device synchronize, printed as one ``PROF`` dict. Does
+    nothing when the variable is unset."""
+
+    def __init__(self, device):
+        self.on = bool(os.environ.get("RXGB_PROFILE_ENGINE"))
+        self.cuda = device.type == "cuda"
+        self.phases = {}
+        self.last = None
+        self.tick(None)
+
+    def tick(self, name):
+        if not self.on:
+            return
+        if self.cuda:
+            torch.cuda.synchronize()
+        now = time.perf_counter()
+        if self.last is not None:
+            self.phases[name] = self.phases.get(name, 0.0) + now - self.last
+        self.last = now
+
+    def report(self):
+        if self.on:
+            print("PROF", {k: round(v * 1000, 2)
+                           for k, v in self.phases.items()}, flush=True)
+
+
+class _TreeGrow:
+    """What the per-depth steps of one depthwise tree share."""
+
+    def __init__(self, it, cls, route, scale_g, scale_h, feat_mask, ridx,
+                 gseg, prof):
+        self.it, self.cls, self.route = it, cls, route
+        self.scale_g, self.scale_h = scale_g, scale_h
+        self.feat_mask = feat_mask  # colsample_bytree gate, or None
+        # row ids and their segment-ordered gradient pairs: the partition
+        # scatter permutes both each depth, so no per-depth gather pass
+        self.ridx, self.gseg = ridx, gseg
+        # the ping-pong ridx buffers exist ONLY for the one-sync loop - the
+        # 2-sync path reassigns ridx to fresh clones each depth, which
+        # would leave buffer 0 stale for the margin update
+        self.ridx_bufs = (
+            [ridx, torch.empty_like(ridx)] if route.use_fused_loop else None
+        )
+        self.cur_buf = 0
+        self.prev_hist: Optional[torch.Tensor] = None
+        self.enq_pull = None  # pinned pull slots of the whole-tree enqueue
+        self.prof = prof
+        self.ta = None  # _TreeArrays the levels write into
+        self.cuts = None  # host copies of (cuts_flat, cut_ptr)
+        # (constraint per feature, scale_g, scale_h, lambda, alpha) for
+        # _Frontier.children, or None without monotone constraints
+        self.mono = None
+
+    def flip(self):
+        """A partition read ``cur_buf`` and wrote the other buffer: make
+        that one current and return the one that was read."""
+        read = self.cur_buf
+        self.cur_buf = 1 - read
+        return read
+
+
+def _hip():
+    """The loaded HIP extension, for the bindings ``ops`` does not wrap."""
+    from xgboost_ray_amd.ops import gpu
+
+    return gpu._load()
 
 
 def _quant_scale(mx: float) -> float:
@@ -1083,53 +1358,31 @@ class BoostingEngine:
                         m[i, f] = 1
         return torch.from_numpy(m)
 
-    def _grow_tree(
-        self, gpair: torch.Tensor, it: int, cls: int, ptree: int = 0
-    ) -> Tree:
-        import os as _os
-        import time as _time
+    def _or_empty(self, t, dtype, shape=(0,)):
+        """``t`` on the device as ``dtype``, or the empty placeholder the
+        C++ entry points take for "absent"."""
+        if t is None:
+            return torch.zeros(shape, dtype=dtype, device=self.device)
+        return t.to(self.device).to(dtype).contiguous()
 
-        _prof = _os.environ.get("RXGB_PROFILE_ENGINE")
-        _t = {}
+    def _gated_feat_bins(self, mask):
+        """Per-feature bin counts with the features outside ``mask`` zeroed
+        (a feature without bins offers no split)."""
+        if mask is None:
+            return self.feat_bins
+        return torch.where(
+            mask, self.feat_bins, torch.zeros_like(self.feat_bins)
+        )
 
-        def _tick(name, _last=[None]):
-            if not _prof:
-                return
-            if self.device.type == "cuda":
-                torch.cuda.synchronize()
-            now = _time.perf_counter()
-            if _last[0] is not None:
-                _t[name] = _t.get(name, 0.0) + now - _last[0]
-            _last[0] = now
-
-        _tick(None)
-        self._mvs_ridx = None
-        if (self.p.sampling_method == "gradient_based"
-                and self.p.subsample < 1.0):
-            # sample first: the reweighted pairs are what gets quantised
-            gpair = self._mvs_sample(gpair, it, cls + 101 * ptree)
-            _tick("mvs_sample")
-        gq, scale_g, scale_h = self._quantize(gpair)
-        _tick("quantize")
-        if self._approx:
-            self._resketch(gq)
-            _tick("sketch")
-        self._scale_g_cur = scale_g
-        self._leaf_segs = []
-        self._leaf_nids = []
-        if self.p.grow_policy == "lossguide":
-            self.last_tree_path = "lossguide"
-            return self._grow_tree_lossguide(gq, scale_g, scale_h, it, cls, ptree)
-        ridx = self._sample_rows(it, cls + 101 * ptree)
-        # segment-ordered gradient pairs aligned with ridx; the partition
-        # scatter permutes them each depth, so no per-depth gather pass
-        if ridx.numel() == self.dtrain.n_rows:
+    def _tree_rows(self, gq, it, key):
+        """Row sample of one tree: (row ids, their gradient pairs in that
+        order, global quantized root sums)."""
+        ridx = self._sample_rows(it, key)
+        n_local = int(ridx.numel())
+        if n_local == self.dtrain.n_rows:
             gseg = gq  # identity order (partition clones before writing)
         else:
             gseg = gq[ridx.long()].contiguous()
-        feat_mask = self._sample_features(it, cls + 101 * ptree)
-        n_local = int(ridx.numel())
-
         if n_local == 0:
             root_sum = torch.zeros(2, dtype=torch.int64, device=self.device)
         elif n_local == self.dtrain.n_rows:
@@ -1142,686 +1395,14 @@ class BoostingEngine:
             root_sum = gq[ridx.long()].sum(dim=0, dtype=torch.int64)
         if self.coll.is_distributed:
             self.coll.allreduce_(root_sum)
+        return ridx, gseg, root_sum
 
-        # ---- SoA tree storage (grow-doubling numpy arrays; the previous
-        # python-list-per-field representation plus _Node objects cost
-        # ~8 ms/round of host bookkeeping at depth 12 / 8191 nodes)
-        ta = _TreeArrays(max(64, 2 ** min(self.p.max_depth + 2, 16)))
-        cuts_flat_cpu = self.dtrain.cuts.cuts_flat.cpu().numpy()
-        cut_ptr_cpu = self.dtrain.cuts.cut_ptr.cpu().numpy()
-        track_paths = self.interaction_sets is not None
-        mono_np = (
-            self.mono.cpu().numpy().astype(np.int64)
-            if self.mono is not None else None
-        )
-
-        # ---- SoA frontier: one numpy array per field. Children are
-        # always appended as (left, right) pairs, so siblings sit at
-        # positions 2i / 2i+1 and the build/derive pairing vectorizes.
-        fr_nid = np.zeros(1, np.int64)
-        fr_start = np.zeros(1, np.int64)
-        fr_count = np.array([n_local], np.int64)
-        fr_pslot = np.zeros(1, np.int64)
-        fr_wlo = np.full(1, -np.inf)
-        fr_whi = np.full(1, np.inf)
-        fr_paths = [()] if track_paths else None
-
-        import os as _os2
-
-        # single-sync fused loop decision is per-tree (see the in-loop
-        # comment); the ping-pong ridx buffers exist ONLY for it - the
-        # 2-sync path reassigns ridx to fresh clones each depth, which
-        # would leave buffer 0 stale for the margin update
-        use_fused_loop = (
-            self.device.type == "cuda"
-            and _os2.environ.get("RXGB_ONE_SYNC", "1") != "0"
-        )
-        # row-order finish (GPU, per tree like RXGB_ONE_SYNC): the margin
-        # update is one apply_tree_binned walk over the binned matrix in
-        # row order, so the last level launches no partition at all - its
-        # children are leaves, and nothing but the scattered per-segment
-        # margin update ever read the permuted ridx/gseg or the child row
-        # counts. Adaptive objectives (reg:quantileerror) need the
-        # per-leaf row lists and keep the legacy finish.
-        # RXGB_ROW_FINISH=0 restores the legacy finish exactly; =2 lifts
-        # the row-stride rule (measurement only).
-        _rf = _os2.environ.get("RXGB_ROW_FINISH", "1")
-        row_finish = (
-            self.device.type == "cuda"
-            and not self._adaptive
-            and _rf != "0"
-            and (_rf == "2"
-                 or self.dtrain.bins.stride(0) <= _ROW_FINISH_MAX_STRIDE)
-        )
-        # fused per-depth glue (GPU, per tree like RXGB_ONE_SYNC): the
-        # sibling histograms are derived inside the split scan, the
-        # per-node reduce and the partition plan are one kernel, the
-        # partition needs no zero fills and one pull brings
-        # {splits | left counts} to the host. RXGB_FUSED_GLUE=0 restores
-        # the separate torch/kernel composition exactly.
-        fused_glue = (
-            self.device.type == "cuda"
-            and _os2.environ.get("RXGB_FUSED_GLUE", "1") != "0"
-        )
-        ridx_bufs = None
-        cur_buf = 0
-        if use_fused_loop:
-            ridx_bufs = [ridx, torch.empty_like(ridx)]
-        # whole-tree enqueue (GPU, per tree like its neighbours): ONE call
-        # puts every level's launches on the stream - depth d+1 reads its
-        # frontier from what a device kernel planned at depth d - and the
-        # loop below only replays each depth's bookkeeping from that
-        # depth's pinned pull, behind the GPU. Taken only where no
-        # per-depth host input exists (no monotone / interaction
-        # constraints, no per-level or per-node column sampling, single
-        # process) and the frontier bound 2^depth fits the single-
-        # workgroup plan kernels. RXGB_TREE_ENQUEUE=0 restores the
-        # per-depth loop exactly.
-        tree_enq = (
-            use_fused_loop and row_finish and fused_glue
-            and _os2.environ.get("RXGB_TREE_ENQUEUE", "1") != "0"
-            and _os2.environ.get("RXGB_DEPTH_STEP") != "1"
-            and not self.coll.is_distributed
-            and self.mono is None
-            and self.interaction_sets is None
-            and self.p.colsample_bylevel >= 1.0
-            and self.p.colsample_bynode >= 1.0
-            and 1 <= self.p.max_depth <= 10
-            and n_local > 0
-        )
-        if tree_enq:
-            from xgboost_ray_amd.ops import gpu as _gpu
-
-            tree_enq = bool(_gpu._load().tree_enqueue_config(
-                self.dtrain.bins, self.n_bins)[0])
-        self.last_tree_path = "enqueue" if tree_enq else "per_depth"
-        enq_pull = None
-        if tree_enq:
-            # the root sums stay on the device and ride the depth-0 pull
-            fr_sumg = np.zeros(1, np.int64)
-            fr_sumh = np.zeros(1, np.int64)
-            fb_tree = self.feat_bins
-            if feat_mask is not None:
-                fb_tree = torch.where(
-                    feat_mask, self.feat_bins,
-                    torch.zeros_like(self.feat_bins),
-                )
-            bins_t_t = getattr(self.dtrain, "bins_t", None)
-            if bins_t_t is None:
-                bins_t_t = torch.zeros(0, dtype=torch.uint8,
-                                       device=self.device)
-            enq_pull = _gpu._load().tree_enqueue(
-                self.dtrain.bins, bins_t_t, gseg, ridx_bufs[0],
-                ridx_bufs[1], root_sum,
-                self.p.max_depth,
-                fb_tree.to(self.device).to(torch.int32).contiguous(),
-                scale_g, scale_h, self.p.reg_lambda, self.p.reg_alpha,
-                self.p.gamma, self.p.min_child_weight, self.n_bins,
-            ).numpy()
-        else:
-            fr_sumg = np.array([int(root_sum[0])], np.int64)
-            fr_sumh = np.array([int(root_sum[1])], np.int64)
-
-        lam = float(self.p.reg_lambda)
-        alpha = float(self.p.reg_alpha)
-        prev_all_hist: Optional[torch.Tensor] = None
-        for depth in range(self.p.max_depth):
-            nF = fr_nid.size
-            if nF == 0:
-                break
-            # ---- build order: per sibling pair build the globally
-            # smaller child (quantized hessian sum as the size proxy -
-            # identical on every rank; local counts are not), derive the
-            # sibling by subtraction. Built block = contiguous leading
-            # slice (one AllReduce, batched subtraction for the rest).
-            if depth == 0:
-                order_idx = np.zeros(1, np.int64)
-                K = 1
-                derive_pslot = np.zeros(0, np.int64)
-                derive_sib_pos = np.zeros(0, np.int64)
-            else:
-                ia = np.arange(0, nF, 2)
-                ib = ia + 1
-                small_is_a = fr_sumh[ia] <= fr_sumh[ib]
-                idx_small = np.where(small_is_a, ia, ib)
-                idx_big = np.where(small_is_a, ib, ia)
-                order_idx = np.concatenate([idx_small, idx_big])
-                K = idx_small.size
-                derive_pslot = fr_pslot[idx_big]
-                derive_sib_pos = np.arange(K, dtype=np.int64)
-
-            # scan-slot order: built block first, derived siblings after
-            nid_ord = fr_nid[order_idx]
-            start_ord = fr_start[order_idx]
-            count_ord = fr_count[order_idx]
-            sumg_ord = fr_sumg[order_idx]
-            sumh_ord = fr_sumh[order_idx]
-            wlo_ord = fr_wlo[order_idx]
-            whi_ord = fr_whi[order_idx]
-            paths_ord = (
-                [fr_paths[i] for i in order_idx] if track_paths else None
-            )
-
-            starts = torch.from_numpy(np.ascontiguousarray(start_ord[:K]))
-            counts = torch.from_numpy(np.ascontiguousarray(count_ord[:K]))
-            KK = sumg_ord.size
-            nd = derive_sib_pos.size
-
-            # feature gate needed by both the python path and depth_step
-            fb = self.feat_bins
-            mask = feat_mask
-            if self.p.colsample_bylevel < 1.0:
-                lvl_mask = self._sample_features(it, cls, level=depth)
-                mask = lvl_mask if mask is None else (mask & lvl_mask)
-            if mask is not None and not tree_enq:
-                fb = torch.where(
-                    mask, self.feat_bins, torch.zeros_like(self.feat_bins)
-                )
-            allowed_m = (
-                self._allowed_mask(paths_ord) if track_paths else None
-            )
-            if self.p.colsample_bynode < 1.0:
-                # per-node feature sampling (xgboost colsample_bynode):
-                # deterministic in (seed, iteration, class, depth) and
-                # in scan-slot order, so every rank draws the same masks
-                node_m = self._bynode_mask(KK, it, cls, depth)
-                allowed_m = (
-                    node_m if allowed_m is None
-                    else (allowed_m.to(torch.uint8) & node_m)
-                )
-
-            F = self.dtrain.n_features
-            # (the whole-tree enqueue owns its two ping-pong histograms)
-            all_hist = None if tree_enq else torch.empty(
-                (nF, F, self.n_bins, 2), dtype=torch.int64, device=self.device
-            )
-
-            # depth_step (one C++ call per depth) measures SLOWER than
-            # the python-orchestrated fused loop in a same-box
-            # interleaved A/B: 2.75-2.96 vs 2.53-2.62 ms/round with the
-            # fused glue in both arms (3.23-3.36 vs 3.20-3.21 before the
-            # row-order finish and the fused glue). Per-depth
-            # python/torch dispatch is not on the critical path, and
-            # depth_step still partitions the last level, which the
-            # row-order finish skips in the python loop. Kept opt-in
-            # (RXGB_DEPTH_STEP=1).
-            use_depth_step = (
-                use_fused_loop and not self.coll.is_distributed
-                and _os2.environ.get("RXGB_DEPTH_STEP") == "1"
-            )
-            # row-order finish: this level's children are leaves, so only
-            # the histogram, the scan and the split pull run for it
-            last_level = (
-                row_finish and not use_depth_step
-                and depth == self.p.max_depth - 1
-            )
-            if tree_enq:
-                # everything is already on the stream: wait for THIS
-                # depth's pull (its own pinned slot and event) and replay
-                # it while the GPU runs the deeper levels
-                _gpu._load().tree_enqueue_wait(depth)
-                KKb = 1 << depth  # the slot is laid out on the bound
-                if depth == 0:
-                    fr_sumg[0] = sumg_ord[0] = enq_pull[0]
-                    fr_sumh[0] = sumh_ord[0] = enq_pull[1]
-                arr = enq_pull[2 + 7 * (KKb - 1): 2 + 7 * (2 * KKb - 1)]
-                pk = arr[: 6 * KK].reshape(KK, 6)
-                gain, bfeat, bbin, bdl, blg, blh = _unpack_splits(pk)
-                use_fused = not last_level
-                lc_full = None
-                if use_fused:
-                    lc_full = arr[6 * KKb: 6 * KKb + KK].copy()
-                    depth_in_buf = cur_buf
-                    cur_buf = 1 - cur_buf
-                _tick("scan_pull")
-                return_to_decode = True
-            elif use_depth_step:
-                # one C++ call per depth: stage + zero + hist + derive +
-                # scan + device-planned partition + pull + scatter. The
-                # ~30 per-depth python/torch dispatches were ~0.8 ms of
-                # wall per round at depth 8.
-                dm_t = torch.from_numpy(
-                    np.concatenate(
-                        [sumg_ord, sumh_ord, start_ord, count_ord,
-                         derive_pslot, derive_sib_pos]
-                    )
-                )
-                # C++ find_splits takes raw pointers: everything must
-                # already be the right dtype ON DEVICE
-                mono_t = (
-                    self.mono.to(self.device).to(torch.int8)
-                    if self.mono is not None
-                    else torch.zeros(0, dtype=torch.int8,
-                                     device=self.device)
-                )
-                bounds_t = (
-                    torch.from_numpy(np.ascontiguousarray(
-                        np.stack([wlo_ord, whi_ord], axis=1)
-                    )).to(self.device)
-                    if self.mono is not None
-                    else torch.zeros((0, 2), dtype=torch.float64,
-                                     device=self.device)
-                )
-                allowed_t = (
-                    allowed_m.to(self.device).to(torch.uint8).contiguous()
-                    if allowed_m is not None
-                    else torch.zeros(0, dtype=torch.uint8,
-                                     device=self.device)
-                )
-                bins_t_t = getattr(self.dtrain, "bins_t", None)
-                if bins_t_t is None:
-                    bins_t_t = torch.zeros(0, dtype=torch.uint8,
-                                           device=self.device)
-                gseg_in = (
-                    gseg if gseg is not None
-                    else torch.zeros((0, 2), dtype=torch.int32,
-                                     device=self.device)
-                )
-                frontier_rows = int(count_ord.sum())
-                chunk_bound = (frontier_rows + 2047) // 2048 + KK
-                from xgboost_ray_amd.ops import gpu as _gpu
-
-                ridx, gseg, pull = _gpu._load().depth_step(
-                    self.dtrain.bins, bins_t_t, gseg_in, ridx,
-                    ridx_bufs[1 - cur_buf],
-                    prev_all_hist if prev_all_hist is not None
-                    else all_hist,
-                    all_hist, dm_t, KK, int(nd), K, starts, counts,
-                    fb.to(self.device).to(torch.int32), scale_g,
-                    scale_h, self.p.reg_lambda,
-                    self.p.reg_alpha, self.p.gamma,
-                    self.p.min_child_weight, mono_t, bounds_t,
-                    allowed_t, self.n_bins, chunk_bound, fused_glue,
-                )
-                depth_in_buf = cur_buf
-                cur_buf = 1 - cur_buf
-                _tick("scan")
-                _gpu._load().wait_pull_event()
-                arr = pull[: 7 * KK].numpy()
-                pk = arr[: 6 * KK].reshape(KK, 6)
-                gain, bfeat, bbin, bdl, blg, blh = _unpack_splits(pk)
-                lc_full = arr[6 * KK : 7 * KK].copy()
-                use_fused = True
-                _tick("scan_pull")
-                return_to_decode = True
-            else:
-                return_to_decode = False
-
-            if not return_to_decode:
-                hist = all_hist[:K]  # built block (contiguous slice)
-                hist.zero_()  # derived rows overwritten by the sub
-                overlap = self.coll.is_distributed and (
-                    (
-                        self.device.type == "cuda"
-                        and self.dtrain.bins.stride(0) % 16 == 0
-                        and F > 16
-                    )
-                    or _os2.environ.get("RXGB_FORCE_OVERLAP_ALLREDUCE") == "1"
-                )
-                if overlap:
-                    # overlap the RCCL AllReduce of each finished feature block
-                    # with the build of the next (BASELINE north-star: side-
-                    # stream collective over xGMI behind the histogram build)
-                    n_chunks = min(4, (F + 31) // 32)
-                    step = ((F + n_chunks - 1) // n_chunks + 15) // 16 * 16
-                    pending = []
-                    f0 = 0
-                    while f0 < F:
-                        f1 = min(f0 + step, F)
-                        ops.build_histogram(
-                            self.dtrain.bins, gseg, ridx, starts, counts,
-                            self.n_bins, f_range=(f0, f1), out=hist,
-                            pregathered=True,
-                        )
-                        sl = hist[:, f0:f1].contiguous()
-                        pending.append((self.coll.allreduce_async(sl), sl, f0, f1))
-                        f0 = f1
-                    for h, sl, c0, c1 in pending:
-                        h.wait()
-                        hist[:, c0:c1].copy_(sl)
-                else:
-                    ops.build_histogram(
-                        self.dtrain.bins, gseg, ridx, starts, counts,
-                        self.n_bins, out=hist, pregathered=True,
-                    )
-                    _tick("hist")
-                    if self.coll.is_distributed:
-                        self.coll.allreduce_(hist)
-                _tick("allreduce")
-                # ONE H2D for this depth's control data (layout in comment
-                # above depth_step)
-                if self.device.type == "cuda":
-                    depth_meta = self._stage_i64(
-                        np.concatenate(
-                            [sumg_ord, sumh_ord, start_ord, count_ord,
-                             derive_pslot, derive_sib_pos]
-                        ),
-                        "depth_meta",
-                    )
-                    pg, ph = depth_meta[:KK], depth_meta[KK : 2 * KK]
-                    d_starts = depth_meta[2 * KK : 3 * KK]
-                    d_counts = depth_meta[3 * KK : 4 * KK]
-                    pslots = depth_meta[4 * KK : 4 * KK + nd]
-                    spos = depth_meta[4 * KK + nd :]
-                else:
-                    pg = torch.from_numpy(sumg_ord)
-                    ph = torch.from_numpy(sumh_ord)
-                    pslots = torch.from_numpy(derive_pslot)
-                    spos = torch.from_numpy(derive_sib_pos)
-                derive_kw = {}
-                if nd and fused_glue:
-                    # sibling = parent - built inside the scan kernel,
-                    # which stores the derived rows for the next depth
-                    derive_kw = dict(
-                        prev_hist=prev_all_hist, pslots=pslots, spos=spos
-                    )
-                elif nd:
-                    # sibling = parent - built, batched over all pairs
-                    torch.sub(
-                        prev_all_hist.index_select(0, pslots),
-                        all_hist.index_select(0, spos),
-                        out=all_hist[K:],
-                    )
-                _tick("stack")
-                mono_bounds = None
-                if self.mono is not None:
-                    mono_bounds = torch.from_numpy(
-                        np.ascontiguousarray(
-                            np.stack([wlo_ord, whi_ord], axis=1)
-                        )
-                    )
-                # single-sync fused path (GPU, default): the split scan's
-                # packed output feeds a device-planned partition directly;
-                # ONE pinned D2H brings {splits | left_counts} to the host,
-                # which replays the identical split predicate for
-                # bookkeeping. The pull is enqueued BEFORE the scatter and
-                # the host waits on an inter-launch EVENT, so it wakes
-                # right after count+prefix and every piece of bookkeeping
-                # overlaps the scatter: measured d8 3.56-3.61 vs 3.72-3.73
-                # ms/round for the 2-sync structure (the first version
-                # synced past the scatter and was SLOWER - see
-                # profiles/README.md pass 5/8). RXGB_ONE_SYNC=0 restores
-                # the 2-sync path.
-                use_fused = use_fused_loop and not last_level
-                lc_full = None
-                if use_fused:
-                    packed_dev = ops.find_splits(
-                        all_hist, pg, ph, fb, scale_g, scale_h,
-                        self.p.reg_lambda, self.p.reg_alpha, self.p.gamma,
-                        self.p.min_child_weight, monotone=self.mono,
-                        bounds=mono_bounds, allowed=allowed_m, pull=False,
-                        reduce=not fused_glue, **derive_kw,
-                    )
-                    _tick("scan")
-                    # grid BOUND: every split node adds at most one
-                    # partial chunk (PART_CHUNK = 2048 rows/workgroup)
-                    frontier_rows = int(count_ord.sum())
-                    chunk_bound = (frontier_rows + 2047) // 2048 + KK
-                    # fused glue: packed_dev is the (node, feature) scan
-                    # tuple, reduced inside the partition's plan kernel
-                    part_fn = (
-                        ops.partition_rows_from_kf if fused_glue
-                        else ops.partition_rows_from_packed
-                    )
-                    part_kw = {} if fused_glue else {"fused_glue": False}
-                    ridx, gseg, pull, pull_ev = (
-                        part_fn(
-                            self.dtrain.bins, ridx, d_starts, d_counts,
-                            packed_dev, gseg,
-                            getattr(self.dtrain, "bins_t", None),
-                            chunk_bound,
-                            ridx_dest=ridx_bufs[1 - cur_buf],
-                            **part_kw,
-                        )
-                    )
-                    depth_in_buf = cur_buf
-                    cur_buf = 1 - cur_buf
-                    # event recorded between the pull D2H and the scatter:
-                    # the host wakes before the scatter and every piece of
-                    # bookkeeping below overlaps it
-                    pull_ev.synchronize()
-                    arr = pull[: 7 * KK].numpy()
-                    pk = arr[: 6 * KK].reshape(KK, 6)
-                    gain, bfeat, bbin, bdl, blg, blh = _unpack_splits(pk)
-                    lc_full = arr[6 * KK : 7 * KK].copy()
-                    _tick("scan_pull")
-                else:
-                    best = ops.find_splits(
-                        all_hist,
-                        pg,
-                        ph,
-                        fb,
-                        scale_g,
-                        scale_h,
-                        self.p.reg_lambda,
-                        self.p.reg_alpha,
-                        self.p.gamma,
-                        self.p.min_child_weight,
-                        monotone=self.mono,
-                        bounds=mono_bounds,
-                        allowed=allowed_m,
-                        **derive_kw,
-                    )
-                    _tick("scan")
-                    gain = best["gain"]
-                    _tick("scan_pull")
-                    bfeat = best["feature"]
-                    bbin = best["bin"]
-                    bdl = best["default_left"]
-                    blg = best["left_g"]
-                    blh = best["left_h"]
-
-            # ---- vectorized split/leaf decision for the whole frontier
-            splits_ok = (gain > 0) & (bfeat >= 0) & np.isfinite(gain)
-            okf = np.nonzero(splits_ok)[0]  # ascending == scan-slot order
-            leaf_idx = np.nonzero(~splits_ok)[0]
-            n_split = int(okf.size)
-
-            if n_split == 0:
-                if leaf_idx.size:
-                    self._finalize_leaves_soa(
-                        ta, nid_ord[leaf_idx], sumg_ord[leaf_idx],
-                        sumh_ord[leaf_idx], start_ord[leaf_idx],
-                        count_ord[leaf_idx], wlo_ord[leaf_idx],
-                        whi_ord[leaf_idx], scale_h,
-                        parity=(depth_in_buf if use_fused else 0),
-                    )
-                fr_nid = np.zeros(0, np.int64)
-                break
-
-            # launch the partition's count+prefix FIRST (GPU): the leaf
-            # finalization and tree-array writes below then run on the
-            # host while those kernels execute, and the children
-            # bookkeeping after finish() overlaps the scatter
-            sf32 = bfeat[okf].astype(np.int32)
-            sb32 = bbin[okf].astype(np.int32)
-            sdl8 = bdl[okf].astype(np.uint8)
-            part_ctx = None
-            if (lc_full is None and self.device.type == "cuda"
-                    and not last_level):
-                part_ctx = ops.partition_begin(
-                    self.dtrain.bins,
-                    ridx,
-                    torch.from_numpy(np.ascontiguousarray(start_ord[okf])),
-                    torch.from_numpy(np.ascontiguousarray(count_ord[okf])),
-                    torch.from_numpy(sf32),
-                    torch.from_numpy(sb32),
-                    torch.from_numpy(sdl8),
-                    gpair_seg=gseg,
-                    bins_t=getattr(self.dtrain, "bins_t", None),
-                )
-
-            if leaf_idx.size:
-                self._finalize_leaves_soa(
-                    ta, nid_ord[leaf_idx], sumg_ord[leaf_idx],
-                    sumh_ord[leaf_idx], start_ord[leaf_idx],
-                    count_ord[leaf_idx], wlo_ord[leaf_idx],
-                    whi_ord[leaf_idx], scale_h,
-                    parity=(depth_in_buf if use_fused else 0),
-                )
-
-            # child ids in scan-slot order (matches the sequential
-            # numbering the list-based builder produced)
-            base = ta.n
-            lids = base + 2 * np.arange(n_split, dtype=np.int64)
-            ta.ensure(base + 2 * n_split)
-            nids_ok = nid_ord[okf]
-            f_ok = bfeat[okf].astype(np.int64)
-            b_ok = bbin[okf].astype(np.int64)
-            # split after bin b: left iff bin <= b; bin b covers
-            # [cut[b-1], cut[b]) so "bin <= b" <=> v < cut[b] = thr.
-            thr_ok = cuts_flat_cpu[cut_ptr_cpu[f_ok] + b_ok].astype(
-                np.float64
-            )
-            ta.feat[nids_ok] = f_ok
-            ta.thr[nids_ok] = thr_ok
-            ta.split_bin[nids_ok] = b_ok
-            ta.left[nids_ok] = lids
-            ta.dl[nids_ok] = bdl[okf]
-            ta.gain[nids_ok] = gain[okf].astype(np.float64)
-            ta.cover[nids_ok] = sumh_ord[okf].astype(np.float64) / scale_h
-            ta.parent[lids] = nids_ok
-            ta.parent[lids + 1] = nids_ok
-            ta.n = base + 2 * n_split
-
-            _tick("tree_host")
-            if lc_full is not None:
-                # fused path: the partition already ran on device; its
-                # per-split-node left counts rode the single pull, in
-                # the same ascending-okf order the plan kernel compacted
-                lc = lc_full[:n_split].astype(np.int64)
-            elif last_level:
-                # no partition ran: the leaf children's segment starts and
-                # counts below are placeholders nothing reads
-                lc = np.zeros(n_split, np.int64)
-            elif part_ctx is not None:
-                ridx, left_counts, gseg = ops.partition_finish(part_ctx)
-                lc = left_counts.numpy().astype(np.int64)
-            else:
-                sstarts = torch.from_numpy(
-                    np.ascontiguousarray(start_ord[okf])
-                )
-                scounts = torch.from_numpy(
-                    np.ascontiguousarray(count_ord[okf])
-                )
-                ridx, left_counts, gseg = ops.partition_rows(
-                    self.dtrain.bins,
-                    ridx,
-                    sstarts,
-                    scounts,
-                    torch.from_numpy(sf32),
-                    torch.from_numpy(sb32),
-                    torch.from_numpy(sdl8),
-                    gpair_seg=gseg,
-                    bins_t=getattr(self.dtrain, "bins_t", None),
-                )
-                lc = left_counts.cpu().numpy().astype(np.int64)
-            _tick("partition")
-            l_start = start_ord[okf]
-            l_sumg = blg[okf]
-            l_sumh = blh[okf]
-            r_start = l_start + lc
-            r_count = count_ord[okf] - lc
-            r_sumg = sumg_ord[okf] - l_sumg
-            r_sumh = sumh_ord[okf] - l_sumh
-
-            # monotone child bounds (exact op order of the scalar path)
-            wlo_p = wlo_ord[okf]
-            whi_p = whi_ord[okf]
-            l_wlo, l_whi = wlo_p.copy(), whi_p.copy()
-            r_wlo, r_whi = wlo_p.copy(), whi_p.copy()
-            if mono_np is not None:
-                cvec = mono_np[sf32]
-                act = cvec != 0
-                if act.any():
-                    wl = np.maximum(wlo_p, np.minimum(
-                        whi_p, _calc_weight_vec(
-                            l_sumg / scale_g, l_sumh / scale_h, lam, alpha
-                        )))
-                    wr = np.maximum(wlo_p, np.minimum(
-                        whi_p, _calc_weight_vec(
-                            r_sumg / scale_g, r_sumh / scale_h, lam, alpha
-                        )))
-                    mid = 0.5 * (wl + wr)
-                    pos = act & (cvec > 0)
-                    neg = act & (cvec < 0)
-                    l_whi = np.where(pos, np.minimum(l_whi, mid), l_whi)
-                    r_wlo = np.where(pos, np.maximum(r_wlo, mid), r_wlo)
-                    l_wlo = np.where(neg, np.maximum(l_wlo, mid), l_wlo)
-                    r_whi = np.where(neg, np.minimum(r_whi, mid), r_whi)
-
-            n2 = 2 * n_split
-            fr_nid = np.empty(n2, np.int64)
-            fr_nid[0::2] = lids
-            fr_nid[1::2] = lids + 1
-            fr_start = np.empty(n2, np.int64)
-            fr_start[0::2] = l_start
-            fr_start[1::2] = r_start
-            fr_count = np.empty(n2, np.int64)
-            fr_count[0::2] = lc
-            fr_count[1::2] = r_count
-            fr_sumg = np.empty(n2, np.int64)
-            fr_sumg[0::2] = l_sumg
-            fr_sumg[1::2] = r_sumg
-            fr_sumh = np.empty(n2, np.int64)
-            fr_sumh[0::2] = l_sumh
-            fr_sumh[1::2] = r_sumh
-            fr_pslot = np.empty(n2, np.int64)
-            fr_pslot[0::2] = okf
-            fr_pslot[1::2] = okf
-            fr_wlo = np.empty(n2, np.float64)
-            fr_wlo[0::2] = l_wlo
-            fr_wlo[1::2] = r_wlo
-            fr_whi = np.empty(n2, np.float64)
-            fr_whi[0::2] = l_whi
-            fr_whi[1::2] = r_whi
-            if track_paths:
-                new_paths = []
-                for k_i, f_i in zip(okf.tolist(), sf32.tolist()):
-                    cp = tuple(sorted(set(paths_ord[k_i]) | {int(f_i)}))
-                    new_paths.append(cp)
-                    new_paths.append(cp)
-                fr_paths = new_paths
-            prev_all_hist = all_hist
-
-        # remaining frontier nodes (max depth reached) become leaves
-        if fr_nid.size:
-            self._finalize_leaves_soa(
-                ta, fr_nid, fr_sumg, fr_sumh, fr_start, fr_count,
-                fr_wlo, fr_whi, scale_h, parity=cur_buf,
-            )
-        if self._adaptive and self._leaf_segs:
-            ta.val[np.asarray(self._leaf_nids, np.int64)] = (
-                self._adaptive_leaf_values(
-                    cls,
-                    ridx_bufs[0] if ridx_bufs is not None else ridx,
-                    ridx_bufs[1] if ridx_bufs is not None else None,
-                    [bp for (s, c, v, bp) in self._leaf_segs]
-                    if ridx_bufs is not None else None,
-                )
-            )
-        # leaf margin update: every row's final node is its segment's
-        # node; _finalize_leaves_soa collected (start, count, value) segs
-        leaf_starts = [s for (s, c, v, bp) in self._leaf_segs]
-        leaf_counts = [c for (s, c, v, bp) in self._leaf_segs]
-        leaf_vals = [v for (s, c, v, bp) in self._leaf_segs]
-        leaf_parity = [bp for (s, c, v, bp) in self._leaf_segs]
-        _tick("leaf_host")
-
-        n = ta.n
-        tree = Tree(
-            feat=ta.feat[:n].astype(np.int32),
-            thr=ta.thr[:n].astype(np.float32),
-            left=ta.left[:n].astype(np.int32),
-            default_left=ta.dl[:n].astype(np.uint8),
-            value=ta.val[:n].astype(np.float32),
-            gain=ta.gain[:n].astype(np.float32),
-            cover=ta.cover[:n].astype(np.float32),
-            parent=np.where(
-                ta.parent[:n] < 0, 2147483647, ta.parent[:n]
-            ).astype(np.int32),
-        )
-
+    def _finish_tree(self, tree, split_bin, cls, n_local, row_finish,
+                     ridx, ridx_b=None):
+        """Advance the training margins by the finished tree. ``ridx``
+        (and ``ridx_b``, the second ping-pong buffer) hold the final row
+        order the leaf segments in _leaf_segs index."""
+        mv = self.margin if self.n_class == 1 else self.margin[:, cls]
         if row_finish:
             # one row-order walk of the finished tree over the binned
             # matrix: each row lands in the leaf the partition chose (or,
@@ -1829,10 +1410,8 @@ class BoostingEngine:
             # single f32 add of the same float32(eta * w). Covers the
             # sampled and the unsampled rows alike.
             ops.apply_tree_binned(
-                self.dtrain.bins,
-                self.margin if self.n_class == 1 else self.margin[:, cls],
-                tree.feat, ta.split_bin[:n], tree.left, tree.default_left,
-                tree.value,
+                self.dtrain.bins, mv, tree.feat, split_bin, tree.left,
+                tree.default_left, tree.value,
             )
         elif n_local < self.dtrain.n_rows:
             # row sampling: EVERY row's margin must advance (xgboost
@@ -1842,23 +1421,496 @@ class BoostingEngine:
             # round 2; also broke resume==continuous under subsample).
             # The binned tree walk lands each row in the identical leaf
             # the partition chose, so sampled rows get the same bits.
-            mv = self.margin if self.n_class == 1 else self.margin[:, cls]
             self._add_tree_margin_raw(tree, mv)
-        elif leaf_starts:
+        elif self._leaf_segs:
+            # every row's final node is its segment's node; the leaf
+            # finalization collected (start, count, value, buffer) segs
+            starts, counts, vals, parity = zip(*self._leaf_segs)
             ops.update_margins(
-                self.margin if self.n_class == 1 else self.margin[:, cls],
-                ridx_bufs[0] if ridx_bufs is not None else ridx,
-                torch.tensor(leaf_starts, dtype=torch.int64),
-                torch.tensor(leaf_counts, dtype=torch.int64),
-                np.asarray(leaf_vals, dtype=np.float32),
-                ridx_b=(ridx_bufs[1] if ridx_bufs is not None else None),
-                parity=(leaf_parity if ridx_bufs is not None else None),
+                mv, ridx,
+                torch.tensor(starts, dtype=torch.int64),
+                torch.tensor(counts, dtype=torch.int64),
+                np.asarray(vals, dtype=np.float32),
+                ridx_b=ridx_b,
+                parity=list(parity) if ridx_b is not None else None,
             )
         self._leaf_segs = []
-        _tick("margins")
-        if _prof:
-            print("PROF", {k: round(v*1000, 2) for k, v in _t.items()}, flush=True)
+
+    def _tree_route(self, n_local) -> _Route:
+        """Read the route switches (per tree: tests toggle them inside one
+        process). Each restores its legacy route exactly when set to 0."""
+        gpu = self.device.type == "cuda"
+        env = os.environ.get
+        use_fused_loop = gpu and env("RXGB_ONE_SYNC", "1") != "0"
+        # row-order finish: the margin update is one apply_tree_binned
+        # walk over the binned matrix in row order, so the last level
+        # launches no partition at all - its children are leaves, and
+        # nothing but the scattered per-segment margin update ever read
+        # the permuted ridx/gseg or the child row counts. Adaptive
+        # objectives (reg:quantileerror) need the per-leaf row lists and
+        # keep the legacy finish. RXGB_ROW_FINISH=2 lifts the row-stride
+        # rule (measurement only).
+        rf = env("RXGB_ROW_FINISH", "1")
+        row_finish = (
+            gpu
+            and not self._adaptive
+            and rf != "0"
+            and (rf == "2"
+                 or self.dtrain.bins.stride(0) <= _ROW_FINISH_MAX_STRIDE)
+        )
+        # fused per-depth glue: the sibling histograms are derived inside
+        # the split scan, the per-node reduce and the partition plan are
+        # one kernel, the partition needs no zero fills and one pull
+        # brings {splits | left counts} to the host. RXGB_FUSED_GLUE=0
+        # restores the separate torch/kernel composition.
+        fused_glue = gpu and env("RXGB_FUSED_GLUE", "1") != "0"
+        # depth_step (one C++ call per depth) measures SLOWER than the
+        # python-orchestrated fused loop in a same-box interleaved A/B:
+        # 2.75-2.96 vs 2.53-2.62 ms/round with the fused glue in both
+        # arms (3.23-3.36 vs 3.20-3.21 before the row-order finish and
+        # the fused glue). Per-depth python/torch dispatch is not on the
+        # critical path, and depth_step still partitions the last level,
+        # which the row-order finish skips in the python loop. Kept
+        # opt-in (RXGB_DEPTH_STEP=1).
+        want_depth_step = env("RXGB_DEPTH_STEP") == "1"
+        use_depth_step = (
+            use_fused_loop and not self.coll.is_distributed
+            and want_depth_step
+        )
+        # whole-tree enqueue: ONE call puts every level's launches on the
+        # stream - depth d+1 reads its frontier from what a device kernel
+        # planned at depth d - and the host only replays each depth's
+        # bookkeeping from that depth's pinned pull, behind the GPU.
+        # Taken only where no per-depth host input exists (no monotone /
+        # interaction constraints, no per-level or per-node column
+        # sampling, single process) and the frontier bound 2^depth fits
+        # the single-workgroup plan kernels.
+        tree_enq = (
+            use_fused_loop and row_finish and fused_glue
+            and env("RXGB_TREE_ENQUEUE", "1") != "0"
+            and not want_depth_step
+            and not self.coll.is_distributed
+            and self.mono is None
+            and self.interaction_sets is None
+            and self.p.colsample_bylevel >= 1.0
+            and self.p.colsample_bynode >= 1.0
+            and 1 <= self.p.max_depth <= 10
+            and n_local > 0
+        )
+        if tree_enq:
+            tree_enq = bool(_hip().tree_enqueue_config(
+                self.dtrain.bins, self.n_bins)[0])
+        return _Route(use_fused_loop, row_finish, fused_glue, tree_enq,
+                      use_depth_step)
+
+    def _grow_tree(
+        self, gpair: torch.Tensor, it: int, cls: int, ptree: int = 0
+    ) -> Tree:
+        prof = _PhaseTimer(self.device)
+        key = cls + 101 * ptree  # this tree's row/column sampling stream
+        self._mvs_ridx = None
+        if (self.p.sampling_method == "gradient_based"
+                and self.p.subsample < 1.0):
+            # sample first: the reweighted pairs are what gets quantised
+            gpair = self._mvs_sample(gpair, it, key)
+            prof.tick("mvs_sample")
+        gq, scale_g, scale_h = self._quantize(gpair)
+        prof.tick("quantize")
+        if self._approx:
+            self._resketch(gq)
+            prof.tick("sketch")
+        self._scale_g_cur = scale_g
+        self._leaf_segs = []
+        self._leaf_nids = []
+        if self.p.grow_policy == "lossguide":
+            self.last_tree_path = "lossguide"
+            return self._grow_tree_lossguide(gq, scale_g, scale_h, it, cls, ptree)
+        ridx, gseg, root_sum = self._tree_rows(gq, it, key)
+        feat_mask = self._sample_features(it, key)
+        n_local = int(ridx.numel())
+
+        route = self._tree_route(n_local)
+        self.last_tree_path = "enqueue" if route.tree_enq else "per_depth"
+        st = _TreeGrow(it, cls, route, scale_g, scale_h, feat_mask, ridx,
+                       gseg, prof)
+        st.ta = _TreeArrays(max(64, 2 ** min(self.p.max_depth + 2, 16)))
+        st.cuts = (self.dtrain.cuts.cuts_flat.cpu().numpy(),
+                   self.dtrain.cuts.cut_ptr.cpu().numpy())
+        if self.mono is not None:
+            st.mono = (self.mono.cpu().numpy().astype(np.int64), scale_g,
+                       scale_h, float(self.p.reg_lambda),
+                       float(self.p.reg_alpha))
+        track_paths = self.interaction_sets is not None
+        if route.tree_enq:
+            # the root sums stay on the device and ride the depth-0 pull
+            fr = _Frontier.root(n_local, 0, 0, track_paths)
+            st.enq_pull = self._enqueue_tree(st, root_sum)
+        else:
+            fr = _Frontier.root(n_local, int(root_sum[0]),
+                                int(root_sum[1]), track_paths)
+
+        for depth in range(self.p.max_depth):
+            fr = self._grow_level(st, fr, depth)
+            if fr is None:  # no node of the level split
+                break
+        if fr is not None:
+            # remaining frontier nodes (max depth reached) become leaves
+            self._finalize_leaves_soa(st.ta, fr, None, scale_h,
+                                      parity=st.cur_buf)
+        ridx_a, ridx_b = st.ridx_bufs or (st.ridx, None)
+        if self._adaptive and self._leaf_segs:
+            st.ta.val[np.asarray(self._leaf_nids, np.int64)] = (
+                self._adaptive_leaf_values(
+                    cls, ridx_a, ridx_b,
+                    [bp for (s, c, v, bp) in self._leaf_segs]
+                    if ridx_b is not None else None,
+                )
+            )
+        prof.tick("leaf_host")
+        tree = st.ta.to_tree()
+        self._finish_tree(tree, st.ta.split_bin[: st.ta.n], cls, n_local,
+                          route.row_finish, ridx_a, ridx_b)
+        prof.tick("margins")
+        prof.report()
         return tree
+
+    def _grow_level(self, st, fr, depth):
+        """One depth: best splits of the frontier by the tree's route, leaf
+        and split bookkeeping, and the children as the next frontier (None
+        when no node split)."""
+        route = st.route
+        lvl = fr.in_build_order(depth)
+        fb, allowed_m = self._level_gates(st, lvl, depth)
+        # row-order finish: this level's children are leaves, so only
+        # the histogram, the scan and the split pull run for it
+        last_level = (
+            route.row_finish and not route.use_depth_step
+            and depth == self.p.max_depth - 1
+        )
+        # (the whole-tree enqueue owns its two ping-pong histograms)
+        all_hist = None if route.tree_enq else torch.empty(
+            (lvl.size, self.dtrain.n_features, self.n_bins, 2),
+            dtype=torch.int64, device=self.device,
+        )
+        if route.tree_enq:
+            sp = self._splits_enqueued(st, lvl, depth, last_level)
+        elif route.use_depth_step:
+            sp = self._splits_depth_step(st, lvl, fb, allowed_m, all_hist)
+        else:
+            self._level_histogram(st, lvl, all_hist)
+            sp = self._scan_and_partition(st, lvl, fb, allowed_m, all_hist,
+                                          last_level)
+
+        # ---- vectorized split/leaf decision for the whole frontier
+        splits_ok = (sp.gain > 0) & (sp.feature >= 0) & np.isfinite(sp.gain)
+        okf = np.nonzero(splits_ok)[0]  # ascending == scan-slot order
+        leaf_idx = np.nonzero(~splits_ok)[0]
+        if okf.size == 0:
+            self._finalize_leaves_soa(st.ta, lvl, leaf_idx, st.scale_h,
+                                      parity=sp.in_buf)
+            return None
+
+        sf32 = sp.feature[okf].astype(np.int32)
+        finish_partition = None
+        if sp.left_counts is None and not last_level:
+            # launch the partition's count+prefix FIRST (GPU): the leaf
+            # finalization and tree-array writes below then run on the
+            # host while those kernels execute, and the children
+            # bookkeeping after the finish overlaps the scatter
+            finish_partition = self._deferred_partition(
+                st, lvl, okf, sf32, sp.bin[okf].astype(np.int32),
+                sp.default_left[okf].astype(np.uint8),
+            )
+        self._finalize_leaves_soa(st.ta, lvl, leaf_idx, st.scale_h,
+                                  parity=sp.in_buf)
+        lids = st.ta.record_splits(
+            lvl.nid[okf], sp.feature[okf].astype(np.int64),
+            sp.bin[okf].astype(np.int64), sp.default_left[okf],
+            sp.gain[okf].astype(np.float64),
+            lvl.sumh[okf].astype(np.float64) / st.scale_h, *st.cuts,
+        )
+        st.prof.tick("tree_host")
+        if sp.left_counts is not None:
+            # the partition already ran on device; its per-split-node
+            # left counts rode the single pull, in the same
+            # ascending-okf order the plan kernel compacted
+            lc = sp.left_counts[: okf.size].astype(np.int64)
+        elif last_level:
+            # no partition ran: the leaf children's segment starts and
+            # counts are placeholders nothing reads
+            lc = np.zeros(okf.size, np.int64)
+        else:
+            lc = finish_partition()
+        st.prof.tick("partition")
+        st.prev_hist = all_hist
+        return lvl.children(okf, lids, sf32, lc, sp.left_g[okf],
+                            sp.left_h[okf], st.mono)
+
+    def _level_gates(self, st, lvl, depth):
+        """(per-feature bin counts, [KK, F] uint8 per-node gate or None) of
+        one level: column sampling and interaction constraints."""
+        mask = st.feat_mask
+        if self.p.colsample_bylevel < 1.0:
+            lvl_mask = self._sample_features(st.it, st.cls, level=depth)
+            mask = lvl_mask if mask is None else (mask & lvl_mask)
+        # (the whole-tree enqueue took its gate when it was launched)
+        fb = (self.feat_bins if st.route.tree_enq
+              else self._gated_feat_bins(mask))
+        allowed_m = (
+            self._allowed_mask(lvl.paths) if lvl.paths is not None else None
+        )
+        if self.p.colsample_bynode < 1.0:
+            # per-node feature sampling (xgboost colsample_bynode):
+            # deterministic in (seed, iteration, class, depth) and
+            # in scan-slot order, so every rank draws the same masks
+            node_m = self._bynode_mask(lvl.size, st.it, st.cls, depth)
+            allowed_m = (
+                node_m if allowed_m is None
+                else (allowed_m.to(torch.uint8) & node_m)
+            )
+        return fb, allowed_m
+
+    def _enqueue_tree(self, st, root_sum):
+        """Launch every level of the tree; returns the pinned pull all
+        depths write to (``_splits_enqueued`` reads one slot per depth)."""
+        fb_tree = self._gated_feat_bins(st.feat_mask)
+        return _hip().tree_enqueue(
+            self.dtrain.bins,
+            self._or_empty(getattr(self.dtrain, "bins_t", None),
+                           torch.uint8),
+            st.gseg, st.ridx_bufs[0], st.ridx_bufs[1], root_sum,
+            self.p.max_depth,
+            fb_tree.to(self.device).to(torch.int32).contiguous(),
+            st.scale_g, st.scale_h, self.p.reg_lambda, self.p.reg_alpha,
+            self.p.gamma, self.p.min_child_weight, self.n_bins,
+        ).numpy()
+
+    def _splits_enqueued(self, st, lvl, depth, last_level):
+        """Whole-tree enqueue: everything is already on the stream. Wait
+        for THIS depth's pull (its own pinned slot and event) and decode
+        it while the GPU runs the deeper levels."""
+        _hip().tree_enqueue_wait(depth)
+        KKb = 1 << depth  # the slot is laid out on the bound
+        if depth == 0:
+            lvl.sumg[0] = st.enq_pull[0]
+            lvl.sumh[0] = st.enq_pull[1]
+        arr = st.enq_pull[2 + 7 * (KKb - 1): 2 + 7 * (2 * KKb - 1)]
+        # the last level of the row-order finish was not partitioned
+        sp = _decode_pull(arr, lvl.size, 6 * KKb,
+                          0 if last_level else st.flip(),
+                          with_counts=not last_level)
+        st.prof.tick("scan_pull")
+        return sp
+
+    def _splits_depth_step(self, st, lvl, fb, allowed_m, all_hist):
+        """One C++ call per depth: stage + zero + hist + derive + scan +
+        device-planned partition + pull + scatter. The ~30 per-depth
+        python/torch dispatches were ~0.8 ms of wall per round at depth 8
+        (and still it measures slower: see ``_tree_route``)."""
+        KK, K = lvl.size, lvl.K
+        has_mono = self.mono is not None
+        chunk_bound = (int(lvl.count.sum()) + 2047) // 2048 + KK
+        # C++ find_splits takes raw pointers: everything must already be
+        # the right dtype ON DEVICE
+        st.ridx, st.gseg, pull = _hip().depth_step(
+            self.dtrain.bins,
+            self._or_empty(getattr(self.dtrain, "bins_t", None),
+                           torch.uint8),
+            self._or_empty(st.gseg, torch.int32, (0, 2)),
+            st.ridx, st.ridx_bufs[1 - st.cur_buf],
+            st.prev_hist if st.prev_hist is not None else all_hist,
+            all_hist, torch.from_numpy(lvl.meta()), KK,
+            int(lvl.derive_sib_pos.size), K,
+            torch.from_numpy(np.ascontiguousarray(lvl.start[:K])),
+            torch.from_numpy(np.ascontiguousarray(lvl.count[:K])),
+            fb.to(self.device).to(torch.int32), st.scale_g, st.scale_h,
+            self.p.reg_lambda, self.p.reg_alpha, self.p.gamma,
+            self.p.min_child_weight,
+            self._or_empty(self.mono, torch.int8),
+            self._or_empty(lvl.bounds() if has_mono else None,
+                           torch.float64, (0, 2)),
+            self._or_empty(allowed_m, torch.uint8),
+            self.n_bins, chunk_bound, st.route.fused_glue,
+        )
+        in_buf = st.flip()
+        st.prof.tick("scan")
+        _hip().wait_pull_event()
+        sp = _decode_pull(pull[: 7 * KK].numpy(), KK, 6 * KK, in_buf)
+        st.prof.tick("scan_pull")
+        return sp
+
+    def _level_histogram(self, st, lvl, all_hist):
+        """Build the level's K built histograms into ``all_hist[:K]`` and
+        allreduce them."""
+        K = lvl.K
+        F = self.dtrain.n_features
+        starts = torch.from_numpy(np.ascontiguousarray(lvl.start[:K]))
+        counts = torch.from_numpy(np.ascontiguousarray(lvl.count[:K]))
+        hist = all_hist[:K]  # built block (contiguous slice)
+        hist.zero_()  # derived rows overwritten by the sub
+        overlap = self.coll.is_distributed and (
+            (
+                self.device.type == "cuda"
+                and self.dtrain.bins.stride(0) % 16 == 0
+                and F > 16
+            )
+            or os.environ.get("RXGB_FORCE_OVERLAP_ALLREDUCE") == "1"
+        )
+        if overlap:
+            # overlap the RCCL AllReduce of each finished feature block
+            # with the build of the next (BASELINE north-star: side-
+            # stream collective over xGMI behind the histogram build)
+            n_chunks = min(4, (F + 31) // 32)
+            step = ((F + n_chunks - 1) // n_chunks + 15) // 16 * 16
+            pending = []
+            f0 = 0
+            while f0 < F:
+                f1 = min(f0 + step, F)
+                ops.build_histogram(
+                    self.dtrain.bins, st.gseg, st.ridx, starts, counts,
+                    self.n_bins, f_range=(f0, f1), out=hist,
+                    pregathered=True,
+                )
+                sl = hist[:, f0:f1].contiguous()
+                pending.append((self.coll.allreduce_async(sl), sl, f0, f1))
+                f0 = f1
+            for h, sl, c0, c1 in pending:
+                h.wait()
+                hist[:, c0:c1].copy_(sl)
+        else:
+            ops.build_histogram(
+                self.dtrain.bins, st.gseg, st.ridx, starts, counts,
+                self.n_bins, out=hist, pregathered=True,
+            )
+            st.prof.tick("hist")
+            if self.coll.is_distributed:
+                self.coll.allreduce_(hist)
+        st.prof.tick("allreduce")
+
+    def _scan_and_partition(self, st, lvl, fb, allowed_m, all_hist,
+                            last_level):
+        """Stage the level's control data, derive the sibling histograms,
+        scan for the best splits and - in the one-sync loop - partition
+        the rows by them on the device."""
+        KK, K = lvl.size, lvl.K
+        nd = lvl.derive_sib_pos.size
+        fused_glue = st.route.fused_glue
+        if self.device.type == "cuda":
+            # ONE H2D for this depth's control data
+            depth_meta = self._stage_i64(lvl.meta(), "depth_meta")
+            pg, ph = depth_meta[:KK], depth_meta[KK : 2 * KK]
+            d_starts = depth_meta[2 * KK : 3 * KK]
+            d_counts = depth_meta[3 * KK : 4 * KK]
+            pslots = depth_meta[4 * KK : 4 * KK + nd]
+            spos = depth_meta[4 * KK + nd :]
+        else:
+            pg = torch.from_numpy(lvl.sumg)
+            ph = torch.from_numpy(lvl.sumh)
+            pslots = torch.from_numpy(lvl.derive_pslot)
+            spos = torch.from_numpy(lvl.derive_sib_pos)
+        derive_kw = {}
+        if nd and fused_glue:
+            # sibling = parent - built inside the scan kernel,
+            # which stores the derived rows for the next depth
+            derive_kw = dict(
+                prev_hist=st.prev_hist, pslots=pslots, spos=spos
+            )
+        elif nd:
+            # sibling = parent - built, batched over all pairs
+            torch.sub(
+                st.prev_hist.index_select(0, pslots),
+                all_hist.index_select(0, spos),
+                out=all_hist[K:],
+            )
+        st.prof.tick("stack")
+        scan_args = (
+            all_hist, pg, ph, fb, st.scale_g, st.scale_h,
+            self.p.reg_lambda, self.p.reg_alpha, self.p.gamma,
+            self.p.min_child_weight,
+        )
+        scan_kw = dict(
+            monotone=self.mono,
+            bounds=lvl.bounds() if self.mono is not None else None,
+            allowed=allowed_m, **derive_kw,
+        )
+        if not st.route.use_fused_loop or last_level:
+            # 2-sync / CPU / unpartitioned last level: pull the splits;
+            # the caller partitions by them where children need rows
+            best = ops.find_splits(*scan_args, **scan_kw)
+            st.prof.tick("scan")
+            st.prof.tick("scan_pull")
+            return _LevelSplits(
+                best["gain"], best["feature"], best["bin"],
+                best["default_left"], best["left_g"], best["left_h"],
+                None, 0,
+            )
+        # single-sync fused path (GPU, default): the split scan's
+        # packed output feeds a device-planned partition directly;
+        # ONE pinned D2H brings {splits | left_counts} to the host,
+        # which replays the identical split predicate for
+        # bookkeeping. The pull is enqueued BEFORE the scatter and
+        # the host waits on an inter-launch EVENT, so it wakes
+        # right after count+prefix and every piece of bookkeeping
+        # overlaps the scatter: measured d8 3.56-3.61 vs 3.72-3.73
+        # ms/round for the 2-sync structure (the first version
+        # synced past the scatter and was SLOWER - see
+        # profiles/README.md pass 5/8). RXGB_ONE_SYNC=0 restores
+        # the 2-sync path.
+        packed_dev = ops.find_splits(
+            *scan_args, pull=False, reduce=not fused_glue, **scan_kw
+        )
+        st.prof.tick("scan")
+        # grid BOUND: every split node adds at most one
+        # partial chunk (PART_CHUNK = 2048 rows/workgroup)
+        chunk_bound = (int(lvl.count.sum()) + 2047) // 2048 + KK
+        # fused glue: packed_dev is the (node, feature) scan
+        # tuple, reduced inside the partition's plan kernel
+        part_fn = (
+            ops.partition_rows_from_kf if fused_glue
+            else ops.partition_rows_from_packed
+        )
+        part_kw = {} if fused_glue else {"fused_glue": False}
+        st.ridx, st.gseg, pull, pull_ev = part_fn(
+            self.dtrain.bins, st.ridx, d_starts, d_counts, packed_dev,
+            st.gseg, getattr(self.dtrain, "bins_t", None), chunk_bound,
+            ridx_dest=st.ridx_bufs[1 - st.cur_buf], **part_kw,
+        )
+        in_buf = st.flip()
+        # event recorded between the pull D2H and the scatter:
+        # the host wakes before the scatter and every piece of
+        # bookkeeping in the caller overlaps it
+        pull_ev.synchronize()
+        sp = _decode_pull(pull[: 7 * KK].numpy(), KK, 6 * KK, in_buf)
+        st.prof.tick("scan_pull")
+        return sp
+
+    def _deferred_partition(self, st, lvl, okf, sf32, sb32, sdl8):
+        """Partition the rows of the split slots ``okf`` where the scan
+        did not (2-sync GPU route, CPU). On the GPU the count+prefix
+        kernels are launched here. Returns the function that completes
+        the partition (left-totals pull + scatter; the whole partition on
+        the CPU) and returns the left counts."""
+        args = (
+            self.dtrain.bins, st.ridx,
+            torch.from_numpy(np.ascontiguousarray(lvl.start[okf])),
+            torch.from_numpy(np.ascontiguousarray(lvl.count[okf])),
+            torch.from_numpy(sf32), torch.from_numpy(sb32),
+            torch.from_numpy(sdl8),
+        )
+        kw = dict(gpair_seg=st.gseg,
+                  bins_t=getattr(self.dtrain, "bins_t", None))
+        if self.device.type == "cuda":
+            ctx = ops.partition_begin(*args, **kw)
+
+            def finish():
+                st.ridx, left_counts, st.gseg = ops.partition_finish(ctx)
+                return left_counts.numpy().astype(np.int64)
+        else:
+            def finish():
+                st.ridx, left_counts, st.gseg = ops.partition_rows(
+                    *args, **kw)
+                return left_counts.cpu().numpy().astype(np.int64)
+        return finish
 
     # which loop grew the last tree: "enqueue" (whole-tree enqueue),
     # "per_depth" or "lossguide"
@@ -1867,15 +1919,19 @@ class BoostingEngine:
     _leaf_nids: List[int] = []  # node id of each _leaf_segs entry
 
 
-    def _finalize_leaves_soa(self, ta, nids, sumg, sumh, starts, counts,
-                             wlo, whi, scale_h, parity=0):
-        """SoA leaf finalization: same math/op order as
-        _finalize_leaves_batch, writing into _TreeArrays and collecting
-        (start, count, value) margin segments."""
+    def _finalize_leaves_soa(self, ta, fr, idx, scale_h, parity=0):
+        """Make the nodes ``fr[idx]`` (all of ``fr`` for None) leaves: same
+        math/op order as the scalar _calc_weight, writing into _TreeArrays
+        and collecting (start, count, value, ridx buffer) margin
+        segments."""
+        sel = slice(None) if idx is None else idx
+        nids = fr.nid[sel]
         if nids.size == 0:
             return
-        G = sumg.astype(np.float64) / self._scale_g_cur
-        H = sumh.astype(np.float64) / scale_h
+        starts, counts = fr.start[sel], fr.count[sel]
+        wlo, whi = fr.wlo[sel], fr.whi[sel]
+        G = fr.sumg[sel].astype(np.float64) / self._scale_g_cur
+        H = fr.sumh[sel].astype(np.float64) / scale_h
         lam = self.p.reg_lambda
         alpha = self.p.reg_alpha
         denom = H + lam
@@ -1895,56 +1951,6 @@ class BoostingEngine:
             zip(starts.tolist(), counts.tolist(), v.tolist(),
                 [parity] * int(nids.size))
         )
-
-    def _finalize_leaves_batch(self, nodes, val_l, cover_l, scale_h):
-        """Vectorized _finalize_leaf for a whole frontier (the per-node
-        Python loop was 5.6 ms/round on 4096-leaf depth-12 trees).
-        Same op order as _calc_weight, so values are bit-identical."""
-        if not nodes:
-            return
-        G = np.fromiter(
-            (nd.sum_g for nd in nodes), np.float64, len(nodes)
-        ) / self._scale_g_cur
-        H = np.fromiter(
-            (nd.sum_h for nd in nodes), np.float64, len(nodes)
-        ) / scale_h
-        lam = self.p.reg_lambda
-        alpha = self.p.reg_alpha
-        denom = H + lam
-        Gs = G
-        if alpha > 0:
-            Gs = np.copysign(np.maximum(np.abs(G) - alpha, 0.0), G)
-        w = np.where(denom > 0, -Gs / np.where(denom > 0, denom, 1.0), 0.0)
-        if self.mono is not None:
-            w = np.clip(
-                w,
-                np.fromiter((nd.w_lower for nd in nodes), np.float64,
-                            len(nodes)),
-                np.fromiter((nd.w_upper for nd in nodes), np.float64,
-                            len(nodes)),
-            )
-        if self.p.max_delta_step > 0:
-            w = np.clip(w, -self.p.max_delta_step, self.p.max_delta_step)
-        v = self.p.eta * w
-        segs = self._leaf_segs
-        for nd, vi, Hi in zip(nodes, v.tolist(), H.tolist()):
-            val_l[nd.nid] = vi
-            cover_l[nd.nid] = Hi
-            segs.append((nd.start, nd.count, vi, 0))
-            self._leaf_nids.append(nd.nid)
-
-    def _finalize_leaf(self, nd: _Node, val_l, cover_l, scale_h):
-        G = nd.sum_g / self._scale_g_cur
-        H = nd.sum_h / scale_h
-        w = _calc_weight(G, H, self.p.reg_lambda, self.p.reg_alpha)
-        if self.mono is not None:
-            w = _clamp(w, nd.w_lower, nd.w_upper)
-        if self.p.max_delta_step > 0:
-            w = max(-self.p.max_delta_step, min(self.p.max_delta_step, w))
-        val_l[nd.nid] = self.p.eta * w
-        cover_l[nd.nid] = H
-        self._leaf_segs.append((nd.start, nd.count, self.p.eta * w, 0))
-        self._leaf_nids.append(nd.nid)
 
     # -- evaluation ----------------------------------------------------------
     def eval_sets(self, evals: Sequence[EvalPack], feval=None) -> Dict[str, Dict[str, float]]:
@@ -2081,27 +2087,10 @@ class BoostingEngine:
         identical scan gains, so all ranks grow the same tree."""
         import heapq
 
-        ridx = self._sample_rows(it, cls + 101 * ptree)
-        if ridx.numel() == self.dtrain.n_rows:
-            gseg = gq
-        else:
-            gseg = gq[ridx.long()].contiguous()
+        ridx, gseg, root_sum = self._tree_rows(gq, it, cls + 101 * ptree)
         n_local = int(ridx.numel())
-        if n_local == 0:
-            root_sum = torch.zeros(2, dtype=torch.int64, device=self.device)
-        elif n_local == self.dtrain.n_rows:
-            root_sum = gq.sum(dim=0, dtype=torch.int64)
-        else:
-            root_sum = gq[ridx.long()].sum(dim=0, dtype=torch.int64)
-        if self.coll.is_distributed:
-            self.coll.allreduce_(root_sum)
-
-        feat_mask = self._sample_features(it, cls + 101 * ptree)
-        fb = self.feat_bins
-        if feat_mask is not None:
-            fb = torch.where(
-                feat_mask, self.feat_bins, torch.zeros_like(self.feat_bins)
-            )
+        fb = self._gated_feat_bins(
+            self._sample_features(it, cls + 101 * ptree))
         cuts_flat_cpu = self.dtrain.cuts.cuts_flat.cpu().numpy()
         cut_ptr_cpu = self.dtrain.cuts.cut_ptr.cpu().numpy()
         max_leaves = self.p.max_leaves or (1 << 30)
@@ -2244,9 +2233,6 @@ class BoostingEngine:
             new_vals = self._adaptive_leaf_values(cls, ridx, None, None)
             for nid_i, nv in zip(self._leaf_nids, new_vals.tolist()):
                 val_l[nid_i] = nv
-        leaf_starts = [st for (st, c, v, bp) in self._leaf_segs]
-        leaf_counts = [c for (st, c, v, bp) in self._leaf_segs]
-        leaf_vals = [v for (st, c, v, bp) in self._leaf_segs]
         tree = Tree(
             feat=np.asarray(feat_l, np.int32),
             thr=np.asarray(thr_l, np.float32),
@@ -2259,19 +2245,7 @@ class BoostingEngine:
                 [2147483647 if pp < 0 else pp for pp in parent_l], np.int32
             ),
         )
-        if int(ridx.numel()) < self.dtrain.n_rows:
-            # row sampling: full-row margin advance (see depthwise note)
-            mv = self.margin if self.n_class == 1 else self.margin[:, cls]
-            self._add_tree_margin_raw(tree, mv)
-        elif leaf_starts:
-            ops.update_margins(
-                self.margin if self.n_class == 1 else self.margin[:, cls],
-                ridx,
-                torch.tensor(leaf_starts, dtype=torch.int64),
-                torch.tensor(leaf_counts, dtype=torch.int64),
-                np.asarray(leaf_vals, dtype=np.float32),
-            )
-        self._leaf_segs = []
+        self._finish_tree(tree, None, cls, n_local, False, ridx)
         return tree
 
     def _finalize_leaf_rec(self, rec, val_l, cover_l, scale_h, nid=None):
@@ -2290,10 +2264,6 @@ class BoostingEngine:
 
     # quantization scale of the current tree (set in _grow_tree via _quantize)
     _scale_g_cur: float = 1.0
-
-
-def _clamp(v: float, lo: float, up: float) -> float:
-    return max(lo, min(up, v))
 
 
 def _calc_weight(G: float, H: float, reg_lambda: float, reg_alpha: float) -> float:

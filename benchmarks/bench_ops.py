@@ -623,6 +623,83 @@ def bench_softmax(shapes=((11_000_000, 3), (11_000_000, 10),
     switches(True)
 
 
+def bench_auc_multi(shapes=((11_000_000, 10), (2_000_000, 100)), n_bins=16384,
+                    sweep=True):
+    """``ops.eval_auc_multiclass``: its two kernels apart, the whole op,
+    ``eval_multiclass`` on the same margin as the floor (one pass over
+    [n, K]) and a torch composition of the same contract (float64 softmax,
+    K integer ``scatter_add_``), windows alternating. GB/s is the compulsory
+    traffic over the median: 4Kn read + 2Kn written for the row kernel, 2Kn
+    read (+ 4n per class and plane with weights) for the count kernel."""
+    from xgboost_ray_amd.ops import gpu
+
+    dev = torch.device("cuda")
+
+    def show(name, t, nbytes=None):
+        rate = f"  {nbytes / t[0] / 1e6:8.1f} GB/s" if nbytes else ""
+        print(f"  {name:42s} {t[0]:9.3f} ms  [{t[1]:.3f}, {t[2]:.3f}]{rate}",
+              flush=True)
+
+    for n, K in shapes:
+        gen = torch.Generator(device=dev).manual_seed(11)
+        margin = torch.randn(n, K, device=dev, generator=gen) * 3
+        label = torch.randint(0, K, (n,), device=dev, generator=gen).float()
+        wts = torch.rand(n, device=dev, generator=gen) * 2
+        empty = torch.zeros(0, device=dev)
+        codes = gpu.auc_bin_rows(margin, label, n_bins)
+        hist = torch.zeros((K, 2, n_bins), dtype=torch.int64, device=dev)
+
+        def torch_form(w):
+            def run():
+                p = torch.softmax(margin.double(), dim=1)
+                b = (p * n_bins).long().clamp_(max=n_bins - 1)
+                b += (label.long()[:, None] == torch.arange(
+                    K, device=dev)[None, :]) * n_bins
+                src = (torch.ones(n, dtype=torch.int64, device=dev)
+                       if w is None else
+                       torch.round(w.double() * 2.0 ** 20).long())
+                h = torch.zeros((K, 2 * n_bins), dtype=torch.int64,
+                                device=dev)
+                for k in range(K):
+                    h[k].scatter_add_(0, b[:, k], src)
+                return h
+            return run
+
+        for w, tag in ((None, "unweighted"), (wts, "weighted")):
+            print(f"auc_multi: {n} x {K}, {n_bins} bins, {tag}")
+            wk = empty if w is None else w
+            planes = 1 if w is None else 2
+            ts = _spread_alt([
+                lambda: gpu.auc_bin_rows(margin, label, n_bins),
+                lambda: gpu.auc_count(codes, n, wk, hist),
+                lambda: ops.eval_auc_multiclass(margin, label, w, n_bins),
+                lambda: ops.eval_multiclass(margin, label, w),
+                torch_form(w),
+            ])
+            c_bytes = planes * n * K * (2 + (0 if w is None else 4))
+            show("auc_bin_rows_kernel", ts[0], 6 * n * K + 4 * n)
+            show("auc_count_kernel", ts[1], c_bytes)
+            show("eval_auc_multiclass (whole op)", ts[2],
+                 6 * n * K + 4 * n + c_bytes)
+            show("eval_multiclass (floor: one pass)", ts[3], 4 * n * K + 4 * n)
+            show("torch: f64 softmax + K scatter_add_", ts[4])
+        if sweep:
+            for chunk in (16, 32):
+                for rows in (128, 192, 256):
+                    try:
+                        t = _spread(lambda: gpu.auc_bin_rows(
+                            margin, label, n_bins, chunk, rows))
+                    except RuntimeError:
+                        continue  # this tile does not fit the LDS budget
+                    show(f"auc_bin_rows chunk {chunk} rows {rows}", t)
+            for threads in (256, 512, 1024):
+                for count_rows in (1 << 16, 1 << 18, 1 << 20, 0):
+                    t = _spread(lambda: gpu.auc_count(
+                        codes, n, empty, hist, count_rows, threads))
+                    show(f"auc_count threads {threads} rows {count_rows}", t)
+        del margin, label, wts, codes, hist
+
+
 def bench_survival(sizes=(1_000_000, 10_000_000),
                    train_shape=(2_000_000, 28)):
     """The HIP survival kernels against the torch routes they replace, on the
@@ -946,6 +1023,8 @@ def main():
         return bench_survival()
     if _sys.argv[1:2] == ["softmax"]:
         return bench_softmax()
+    if _sys.argv[1:2] == ["auc_multi"]:
+        return bench_auc_multi()
     if _sys.argv[1:2] == ["rank"]:
         return bench_rank()
     if _sys.argv[1:2] == ["leaf_quantile"]:

@@ -103,6 +103,21 @@ if "--cpu-only" not in sys.argv:
                                  "-Xclang", "-packed-fp32-ops"],
                     },
                 ),
+                # The multiclass AUC kernels, a module of their own with the
+                # flags of the softmax module: their float32 work is the
+                # row maximum.
+                cpp_extension.CUDAExtension(
+                    name="xgboost_ray_amd._hip_auc_ops",
+                    sources=[os.path.join(src_dir, "auc", "auc_ops.hip")],
+                    extra_compile_args={
+                        "cxx": ["-O3", "-std=c++17"],
+                        # -ffp-contract=off: a row's float64 steps are the
+                        # contract's, p * n_bins not fused into a compare
+                        "nvcc": ["-O3", "-std=c++17", "-ffp-contract=off",
+                                 "-Xclang", "-target-feature",
+                                 "-Xclang", "-packed-fp32-ops"],
+                    },
+                ),
                 # The weighted quantile sketch kernels (tree_method="approx"),
                 # a module of their own: integer sums only, so no float flag.
                 cpp_extension.CUDAExtension(

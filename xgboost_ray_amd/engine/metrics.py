@@ -153,13 +153,80 @@ class BinaryError(Metric):
         return float(s[0] / s[1])
 
 
+def _auc_multiclass_stats(margin, label, weight):
+    """Stats of an [n, K] margin: the one-vs-rest score histograms of
+    ``ops.eval_auc_multiclass`` as float64, [pos | neg] per class. A GPU
+    margin takes the HIP kernels; a CPU margin, and RXGB_FUSED_EVAL=0 (which
+    copies the margin to the host: the correctness route, not the fast one),
+    take ``ops.cpu``."""
+    from xgboost_ray_amd import ops
+
+    if _fused_eval_ok(margin, max_dim=2):
+        hist = ops.eval_auc_multiclass(margin, label, weight, _AUC_BINS)
+    else:
+        hist = ops.cpu.eval_auc_multiclass(
+            margin.cpu(), label.cpu(),
+            None if weight is None else weight.cpu(), _AUC_BINS,
+        ).to(margin.device)
+    # kernel layout [neg | pos] -> metric layout [pos | neg]
+    return hist.flip(1).reshape(-1).double()
+
+
+def _binned_roc_auc(pos, neg):
+    # iterate bins ascending: AUC = sum over bins of
+    # neg_below * pos_here + 0.5 * neg_here * pos_here
+    cneg = torch.cumsum(neg, 0) - neg
+    auc = (cneg * pos).sum() + 0.5 * (neg * pos).sum()
+    denom = pos.sum() * neg.sum()
+    return float(auc / denom) if denom > 0 else 0.5
+
+
+def _binned_pr_auc(pos, neg):
+    tot_pos = pos.sum()
+    if float(tot_pos) <= 0:
+        return 0.0
+    # descending-score sweep: cumulative TP/FP from the top bin down
+    tp = torch.flip(torch.cumsum(torch.flip(pos, [0]), 0), [0])
+    fp = torch.flip(torch.cumsum(torch.flip(neg, [0]), 0), [0])
+    recall = tp / tot_pos
+    prec = tp / torch.clamp(tp + fp, min=1e-300)
+    # integrate precision d(recall) over bins, descending threshold:
+    # recall increases as the threshold drops
+    r = torch.flip(recall, [0])
+    p = torch.flip(prec, [0])
+    dr = torch.diff(r, prepend=torch.zeros(1, dtype=r.dtype,
+                                           device=r.device))
+    return float((p * dr).sum())
+
+
+def _one_vs_rest(s, area, empty):
+    """``area(pos, neg)`` of a stats vector: the binary value for one pair of
+    planes; for K pairs the average weighted by each class's positive mass,
+    over the classes that have both positive and negative mass (``empty`` if
+    none has)."""
+    K = s.numel() // (2 * _AUC_BINS)
+    if K <= 1:
+        return area(s[:_AUC_BINS], s[_AUC_BINS:])
+    total = mass = 0.0
+    for c in s.reshape(K, 2, _AUC_BINS):
+        p, n = float(c[0].sum()), float(c[1].sum())
+        if p > 0 and n > 0:
+            total += p * area(c[0], c[1])
+            mass += p
+    return total / mass if mass > 0 else empty
+
+
 class AUC(Metric):
-    """Binned ROC AUC: weighted pos/neg histograms over sigmoid(margin)."""
+    """Binned ROC AUC: weighted pos/neg histograms over sigmoid(margin); for
+    an [n, K] margin the prevalence-weighted one-vs-rest average over the
+    softmax probabilities."""
 
     name = "auc"
     higher_better = True
 
     def local_stats(self, margin, label, weight, qid, obj):
+        if margin.dim() == 2:
+            return _auc_multiclass_stats(margin, label, weight)
         if weight is None and _fused_eval_ok(margin):
             from xgboost_ray_amd.ops import gpu
 
@@ -194,13 +261,7 @@ class AUC(Metric):
         return torch.cat([pos, neg])
 
     def finalize(self, s):
-        pos, neg = s[:_AUC_BINS], s[_AUC_BINS:]
-        # iterate bins ascending: AUC = sum over bins of
-        # neg_below * pos_here + 0.5 * neg_here * pos_here
-        cneg = torch.cumsum(neg, 0) - neg
-        auc = (cneg * pos).sum() + 0.5 * (neg * pos).sum()
-        denom = pos.sum() * neg.sum()
-        return float(auc / denom) if denom > 0 else 0.5
+        return _one_vs_rest(s, _binned_roc_auc, 0.5)
 
 
 class AUCPR(Metric):
@@ -214,22 +275,7 @@ class AUCPR(Metric):
         return AUC.local_stats(self, margin, label, weight, qid, obj)
 
     def finalize(self, s):
-        pos, neg = s[:_AUC_BINS], s[_AUC_BINS:]
-        tot_pos = pos.sum()
-        if float(tot_pos) <= 0:
-            return 0.0
-        # descending-score sweep: cumulative TP/FP from the top bin down
-        tp = torch.flip(torch.cumsum(torch.flip(pos, [0]), 0), [0])
-        fp = torch.flip(torch.cumsum(torch.flip(neg, [0]), 0), [0])
-        recall = tp / tot_pos
-        prec = tp / torch.clamp(tp + fp, min=1e-300)
-        # integrate precision d(recall) over bins, descending threshold:
-        # recall increases as the threshold drops
-        r = torch.flip(recall, [0])
-        p = torch.flip(prec, [0])
-        dr = torch.diff(r, prepend=torch.zeros(1, dtype=r.dtype,
-                                               device=r.device))
-        return float((p * dr).sum())
+        return _one_vs_rest(s, _binned_pr_auc, 0.0)
 
 
 def _fused_multiclass(margin, label, weight):

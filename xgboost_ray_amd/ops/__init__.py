@@ -711,6 +711,40 @@ def eval_multiclass(margin, label, weight=None, **kw):
     return _impl(margin).eval_multiclass(margin, label, weight, **kw)
 
 
+def eval_auc_multiclass(margin, label, weight=None, n_bins=16384, **kw):
+    """int64 [K, 2, n_bins] one-vs-rest score histograms of a multiclass
+    margin, planes [negative | positive] per class: what ``auc`` and
+    ``aucpr`` reduce an [n, K] margin to.
+
+    margin: f32 [n, K] contiguous, K >= 2; label: f32 [n]; weight: f32 [n]
+    or None; 1 <= n_bins <= 16384, anything else raises before any launch.
+    Per row, p_k is the softmax of ``softmax_grad``'s contract in its
+    one-chunk form, for every K: m = max_k x_k (compared in float32),
+    d_k = (double)x_k - (double)m, e_k = exp(d_k), s = sum_k e_k in ascending
+    class order, p_k = e_k / s, nothing contracted. b_k = min(trunc(p_k *
+    n_bins), n_bins - 1), and 0 unless p_k * n_bins >= 1: a NaN row lands in
+    bin 0 of every class and no address depends on a NaN. Row i is a
+    positive of class k iff its label, truncated toward zero as ``.long()``
+    does, equals k; the label is only compared and never forms an address,
+    and outside [0, K) the row is a negative of every class. Each row adds 1
+    to ``hist[k, positive, b_k]`` for every k, or with weights
+    W = llrint((double)w * 2^20); n * 2^20 * max(w) must stay below 2^53
+    (checked on the host, only when weights are given).
+
+    All sums are integer: two launches, any world size and any sharding give
+    equal bytes. On the GPU two kernels run (docs/parity.md "Multiclass AUC
+    on the device"): one pass over the margin writes a u16 code per (class,
+    row), class-major; a grid of row segments x classes counts the codes
+    into LDS histograms. ``max_out_bytes`` (keyword, GPU, default
+    ``ops.gpu.WALK_OUT_BYTES``) bounds the code buffer of one row chunk and
+    ``count_rows`` the rows of a counting workgroup.
+    ``ops.cpu.eval_auc_multiclass`` is the numpy float64 form and the
+    oracle; its integers match the kernels'.
+    """
+    return _impl(margin).eval_auc_multiclass(margin, label, weight, n_bins,
+                                             **kw)
+
+
 # Sorted positions per workgroup of the GPU Cox kernels (asserted equal to
 # the module's on load): the sizes around it are where their paths change
 COX_TILE_ROWS = _cpu.COX_TILE_ROWS

@@ -1120,6 +1120,57 @@ def eval_multiclass(margin, label, weight=None):
         np.array([(w * nll).sum(), (w * wrong).sum(), w.sum()], np.float64))
 
 
+AUC_MAX_BINS = 16384     # a bin is 14 bits of the HIP kernels' u16 code
+AUC_WEIGHT_SCALE = 2.0 ** 20
+
+
+def auc_multiclass_check(n, weight, n_bins):
+    """What ``eval_auc_multiclass`` refuses, on either backend, before any
+    work: a bin count outside [1, AUC_MAX_BINS], and weights whose integer
+    mass n * 2^20 * max |w| could reach 2^53 (NaN weights included)."""
+    if not 1 <= int(n_bins) <= AUC_MAX_BINS:
+        raise ValueError(
+            f"eval_auc_multiclass: n_bins must lie in [1, {AUC_MAX_BINS}], "
+            f"got {n_bins}")
+    if weight is not None and n:
+        bound = float(n) * AUC_WEIGHT_SCALE * float(weight.abs().max())
+        if not bound < 2.0 ** 53:
+            raise ValueError(
+                "eval_auc_multiclass: n * 2^20 * max(weight) must stay below "
+                f"2^53, got {bound:g}")
+
+
+def eval_auc_multiclass(margin, label, weight=None, n_bins=16384):
+    """int64 [K, 2, n_bins] one-vs-rest score histograms, planes [neg | pos]
+    (contract: ``ops.eval_auc_multiclass``). Plain numpy float64, the oracle
+    of the HIP kernels; the integers match theirs."""
+    import numpy as np
+
+    n_bins = int(n_bins)
+    wt = None if weight is None else torch.as_tensor(_as_numpy(weight))
+    auc_multiclass_check(len(label), wt, n_bins)
+    d, e, s, yi = _softmax_rows(margin, label)
+    n, K = e.shape
+    with np.errstate(invalid="ignore"):
+        t = (e / s[:, None]) * float(n_bins)
+        # NaN fails the comparison: bin 0
+        b = np.where(t >= 1.0, np.minimum(np.trunc(t), n_bins - 1),
+                     0).astype(np.int64)
+    if weight is None:
+        W = np.ones(n, np.float64)
+    else:
+        w = np.asarray(_as_numpy(weight), np.float32).astype(np.float64)
+        W = np.rint(w * AUC_WEIGHT_SCALE)  # integers: sums below 2^53 exact
+    hist = np.zeros((K, 2, n_bins), np.int64)
+    for k in range(K):
+        pos = yi == k
+        for plane, rows in ((0, ~pos), (1, pos)):
+            hist[k, plane] = np.bincount(
+                b[rows, k], weights=W[rows], minlength=n_bins
+            ).astype(np.int64)
+    return torch.from_numpy(hist)
+
+
 # --- survival (contract: docs/parity.md "Survival on the device") ----------
 # Float64 torch forms written from the formulae, not from the objective
 # classes; tests/test_survival_ops_cpu.py pins them to those classes.

@@ -405,6 +405,59 @@ def eval_multiclass(margin, label, weight=None, chunk=0, rows=0):
         *_softmax_args(margin, label, weight), int(chunk), int(rows))
 
 
+_auc_ext = None
+
+
+def _load_auc():
+    """The multiclass AUC kernels' module (csrc/auc); required like
+    ``_hip_ops``."""
+    global _auc_ext
+    if _auc_ext is None:
+        _load()  # same build; raises the build hint if nothing is built
+        import importlib
+        from xgboost_ray_amd.ops import cpu
+
+        _auc_ext = importlib.import_module("xgboost_ray_amd._hip_auc_ops")
+        assert _auc_ext.AUC_MAX_BINS == cpu.AUC_MAX_BINS
+    return _auc_ext
+
+
+def auc_bin_rows(margin, label, n_bins, chunk=0, rows=0):
+    """Stage 1 of ``eval_auc_multiclass``: int16 [K, n rounded up to 8], the
+    u16 codes ``bin | positive << 15``, class-major."""
+    return _load_auc().auc_bin_rows(margin, label, int(n_bins), int(chunk),
+                                    int(rows))
+
+
+def auc_count(codes, n, weight, hist, count_rows=0, threads=0):
+    """Stage 2: count the first n codes of every class row into ``hist``
+    (int64 [K, 2, n_bins], accumulated into); ``weight`` f32 [n] or empty."""
+    _load_auc().auc_count(codes, int(n), weight, hist, int(count_rows),
+                          int(threads))
+    return hist
+
+
+def eval_auc_multiclass(margin, label, weight=None, n_bins=16384,
+                        max_out_bytes=None, count_rows=0, chunk=0, rows=0,
+                        threads=0):
+    """Rows are processed in chunks whose u16 code buffer (2 K bytes a row)
+    stays under ``max_out_bytes`` (default WALK_OUT_BYTES); ``count_rows`` is
+    the rows of a counting workgroup. chunk / rows / threads override the
+    kernels' tile constants (benchmarks/bench_ops.py sweeps them)."""
+    from xgboost_ray_amd.ops import cpu
+
+    cpu.auc_multiclass_check(margin.shape[0], weight, n_bins)
+    margin, label, w = _softmax_args(margin, label, weight)
+    n, K = margin.shape
+    hist = torch.zeros((K, 2, int(n_bins)), dtype=torch.int64,
+                       device=margin.device)
+    for s, e in _row_chunks(n, 2 * K, max_out_bytes):
+        codes = auc_bin_rows(margin[s:e], label[s:e], n_bins, chunk, rows)
+        auc_count(codes, e - s, w[s:e] if w.numel() else w, hist, count_rows,
+                  threads)
+    return hist
+
+
 COX_TILE_ROWS = 2048  # checked against the extension's own constant
 _AFT_DIST = {"normal": 0, "logistic": 1, "extreme": 2}
 _survival_ext = None
